@@ -7,7 +7,11 @@ followed by one 50-step classifier-free-guidance edit with attention fusion (Rep
 blend-mask-gated self-attention, th 0.3) -- latents in, latents out (VAE / CLIP / file I/O excluded on both sides,
 SURVEY.md §8d).  value = frames edited per second over the whole job, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ddim-steps T] [--frames F] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ddim-steps T] [--frames F] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
+
+A plain run sets up, warms up, times the K jobs and prints the line (`value`, `ms_per_step` = wall milliseconds of one timed job,
+`ms_per_step_spread`).  `--dump-outputs DIR` writes the edited latents of the last timed job as DIR/edited_latents.npy (float32; the
+inputs are seeded, so two builds can be compared output for output).  `--full` adds everything else the line can carry (below).
 
 N > 1: one rank per GPU over RCCL.  Launched under torch.distributed.run the ranks are taken from the environment; a BARE
 `python bench.py --gpus N` re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -16,10 +20,11 @@ weak scaling; RCCL carries only latents: a weights checksum is broadcast-checked
 over xGMI; no collective inside the UNet).  `--shard frames`: ONE clip's frames split over the ranks (strong scaling;
 GroupNorm / K-V / temporal exchanges, fatezero_amd/dist.py).  With N > 1 the clips line carries `n_ranks_seen` from an RCCL
 all-reduce and a watchdog-guarded `frame_sharded` measurement (one extra job after the clips measurement; `--no-frame-shard-probe`
-skips it).
+skips it; it runs without `--full` only where `--shard auto` may make it the headline: frames >= 2 x GPUs).
 
-Extra JSON fields: `roofline` for the judged kernel (the 64x64-level fused spatio-temporal flash attention, 4096 x 8192 x
-d=40: algorithmic FLOPs / HIP-event time measured live on the launch stream), `rooflines` = the same for the other
+Extra JSON fields of `--full`: `box` / `value_normalised` (the calibration launches and the clock / power sampler),
+`config_faithful_n_edit_2`, `split_mask_job`, `roofline` for the judged kernel (the 64x64-level fused spatio-temporal flash
+attention, 4096 x 8192 x d=40: algorithmic FLOPs / HIP-event time measured live on the launch stream), `rooflines` = the same for the other
 hand-written kernels that matter (3x3 convolutions and projection GEMMs: MFMA; attention-map capture / inject: HBM), and
 `cpu_baseline` (the CPU oracle of the same loop on the host cores, bounded sample).
 """
@@ -839,6 +844,12 @@ def main():
                          "(csrc/peer.hip: no collective call on the data path), 'rccl' = torch.distributed collectives; 'auto' = peer when "
                          "its self-test round trip succeeds on EVERY rank, else rccl (the line says which).  Default rccl: the peer transport "
                          "has met HIP IPC between two processes on one GPU but never xGMI -- opt in with --transport auto / peer")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: box calibration + clock / power sampler, flash event brackets and "
+                         "rooflines, the n_edit = 2 job, the split-mask sweep + job, the kernel-breakdown job, the CPU baseline and (N > 1 "
+                         "over clips) the frame-sharded probe; the --no-* switches then drop single parts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed jobs, write the edited latents of the last one as DIR/edited_latents.npy (float32)")
     ap.add_argument("--peer-heap-gb", type=float, default=2.0, help="symmetric heap per GPU for --transport peer")
     ap.add_argument("--blend-th", type=float, default=None,
                     help="blend_th of the Porsche edit in the TIMED jobs instead of the config's 0.3 (the in-situ PMC pass of scripts/pmc_job.sh "
@@ -880,7 +891,8 @@ def main():
         install_launch_log(K, os.environ["FZ_BENCH_LAUNCHLOG"])
     timer = KernelTimer()
     timer.extra = False
-    install_timers(K, timer)
+    if args.full:
+        install_timers(K, timer)
 
     model_config = None
     if args.cfg1:
@@ -910,7 +922,8 @@ def main():
     if by_frames:
         from fatezero_amd import dist as fz_dist
         pipe.frame_shard, transport_used = make_frame_shard(fz_dist, args.frames, args.transport, args.peer_heap_gb, device)
-    box = measure_box(K, device) if not args.no_box else None  # BEFORE the warm-up: the chip as the job will find it
+    with_box = args.full and not args.no_box
+    box = measure_box(K, device) if with_box else None  # BEFORE the warm-up: the chip as the job will find it
     wsteps = args.warmup_ddim_steps or args.ddim_steps
     for _ in range(args.warmup):
         run_job(pipe, z0, wsteps, device)
@@ -920,8 +933,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    timer.enabled = True
-    sampler = SmiSampler(local_rank).start() if (rank == 0 and not args.no_box) else None
+    timer.enabled = args.full
+    sampler = SmiSampler(local_rank).start() if (rank == 0 and with_box) else None
     barrier()
     t0 = time.perf_counter()
     edited = None
@@ -933,10 +946,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     smi = sampler.stop() if sampler is not None else None
-    box_hot = measure_box(K, device, hot=True) if not args.no_box else None  # straight behind the timed jobs: the chip still in the job's state
+    box_hot = measure_box(K, device, hot=True) if with_box else None  # straight behind the timed jobs: the chip still in the job's state
     per_job_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     n_edit2 = None
-    if args.n_edit == 1 and not args.no_n_edit2_probe and not by_frames:
+    if args.full and args.n_edit == 1 and not args.no_n_edit2_probe and not by_frames:
         # the config-faithful job (1 inversion + BOTH prompts of jeep_posche.yaml), one run after the timed region, reported beside
         # the primary: frames/s = F * n_edit / (t_inversion + sum t_edit)  
         timer.enabled = False
@@ -951,7 +964,7 @@ def main():
                    "what": "1 capture inversion + 2 CFG edits (p2p_config 0: Refine + Reweight + blend, p2p_config 1: Replace + blend)"}
         timer.enabled = True
     split = None
-    if not args.no_kernel_breakdown and not args.cfg1 and not by_frames and not args.no_split_mask:
+    if args.full and not args.no_kernel_breakdown and not args.cfg1 and not by_frames and not args.no_split_mask:
         # a blend threshold under which the masked-inject launches really read stored rows (pick_split_threshold), and ONE job with it,
         # timed like the primary (no event brackets besides the flash ones), beside the config-faithful th = 0.3 of the timed region
         timer.enabled = False
@@ -968,7 +981,7 @@ def main():
                      "what": "the primary job with blend_th raised so that the blend mask SPLITS the self-attention rows (the config's 0.3 "
                              "leaves ~all rows live with procedural weights: its masked-inject launches read no stored map)"}
         timer.enabled = True
-    if not args.no_kernel_breakdown:  # (every rank: a frame-sharded job has collectives inside)
+    if args.full and not args.no_kernel_breakdown:  # (every rank: a frame-sharded job has collectives inside)
         # the other kernels' event brackets (22 k launches per job, one barrier packet each: ~3 % on the job) go on ONE extra job
         # after the timed region; its flash launches are not counted.  It runs with the split threshold: the inject entry then
         # measures launches that read stored rows (every other class launches the same kernels on the same shapes either way)
@@ -991,12 +1004,16 @@ def main():
             edited = torch.cat(gathered, dim=0)
     dt = float(tmax.item())
     finite = bool(torch.isfinite(edited.float()).all())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "edited_latents.npy"), edited.float().cpu().numpy())
 
     line = None
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = (1 if by_frames else world) * args.frames * args.n_edit * args.steps / dt
-        roof, others = rooflines(timer.summary())
+        roof, others = rooflines(timer.summary()) if args.full else (None, None)
         px = 8 * L
         judged = args.frames == 8 and L == 64 and args.ddim_steps == 50 and not args.cfg1
         line = {"metric": "edited frames/sec (8f x 512^2 x 50 DDIM steps: capture inversion + 1 CFG edit, latents in/out)" if judged else
@@ -1035,7 +1052,7 @@ def main():
             line["issue_plans"] = {k: (v if not isinstance(v, list) else v[:4]) for k, v in pipe.unet._issuer.stats.items()}
         if n_edit2 is not None:
             line["config_faithful_n_edit_2"] = n_edit2
-        if not args.no_cpu_baseline and world == 1 and L == 64:  # (the oracle sample is a 512x512 clip)
+        if args.full and not args.no_cpu_baseline and world == 1 and L == 64:  # (the oracle sample is a 512x512 clip)
             try:
                 line["cpu_baseline"] = cpu_baseline(pipe, args.ddim_steps, args.frames, k=args.cpu_k)
                 if args.cpu_cfg1:
@@ -1045,7 +1062,7 @@ def main():
 
     # ---- N > 1, clips mode: one more job with ONE clip's frames split over the ranks (SURVEY 8e's natural split), guarded:
     #      if the exchange path stalls the clips line above is still printed (every rank runs the same watchdog)
-    if dist is not None and not by_frames and not args.no_frame_shard_probe and args.frames >= world:
+    if dist is not None and not by_frames and not args.no_frame_shard_probe and args.frames >= world and (args.full or auto_frames):
         import threading
         done = threading.Lock()
 

@@ -125,7 +125,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) ff_chain_kernel(FcArgs g) {
         // (the compiler's scoreboard must see the row loads retired HERE: with them formally pending it guards every MFMA of the loop with
         //  a counted vmcnt wait that, the DMA of the next stage being younger, drains that DMA early in each iteration)
 #pragma unroll
-        for (int s = 0; s < FC_KS; ++s) asm volatile("" : "+v"(xb[s]));
+        for (int s = 0; s < FC_KS; ++s) FZ_PIN_V(xb[s]);
         issue(0);
 #ifdef FC_TIMING
         long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};

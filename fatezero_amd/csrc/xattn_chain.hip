@@ -210,7 +210,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
         }
         // (retired HERE for the compiler's scoreboard: csrc/ff_chain.hip)
 #pragma unroll
-        for (int s = 0; s < XC_KS; ++s) asm volatile("" : "+v"(xb[s]));
+        for (int s = 0; s < XC_KS; ++s) FZ_PIN_V(xb[s]);
         issue_step(0);
 
         if constexpr (FRONT) {
@@ -326,7 +326,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             // (the row stays 80 registers of packed halves between the sweeps: without the pins the compiler keeps all 160 fp32 conversions
             //  of the first sweep alive for the other two and spills)
 #pragma unroll
-            for (int s = 0; s < XC_KS; ++s) asm volatile("" : "+v"(hv[s]));
+            for (int s = 0; s < XC_KS; ++s) FZ_PIN_V(hv[s]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 float q0 = 0.0f, q1 = 0.0f;
@@ -344,7 +344,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             for (int u = 0; u < 4; ++u) tu[u] = pu[u] + fz_shfl_xor(pu[u], 32);
             const float rstd = 1.0f / sqrtf(pair_sum(tu) * (1.0f / 320.0f) + g.eps1);
 #pragma unroll
-            for (int s = 0; s < XC_KS; ++s) asm volatile("" : "+v"(hv[s]));
+            for (int s = 0; s < XC_KS; ++s) FZ_PIN_V(hv[s]);
 #pragma unroll
             for (int s = 0; s < XC_KS; ++s) {
                 const half8_t gm = *reinterpret_cast<const half8_t*>(cst + (XC_C + 16 * s) * 2);
@@ -357,7 +357,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             }
             }
 #pragma unroll
-            for (int s = 0; s < XC_KS; ++s) asm volatile("" : "+v"(xb[s]));
+            for (int s = 0; s < XC_KS; ++s) FZ_PIN_V(xb[s]);
 #ifdef XC_DEBUG_XN  // trial build: the LayerNorm output leaves through y_ln (the epilogue then skips its own)
 #pragma unroll
             for (int s = 0; s < XC_KS; ++s) fz_st_h8(g.yln + row * XC_C + 16 * s + 8 * hi, xb[s]);
@@ -535,7 +535,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             // sub-step 1 (this wave's: vmcnt(0) + barrier + DMA of sub-step 3), with the loads pinned between the wait and the DMA issue
             fz_wait_vm0();
 #pragma unroll
-            for (int f = 0; f < 6; ++f) asm volatile("" : "+v"(ra[f]));
+            for (int f = 0; f < 6; ++f) FZ_PIN_V(ra[f]);
             fz_barrier_nodrain();
             if (step + 2 < NSTEP) issue_step(step + 2);
             ++step;
@@ -546,7 +546,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             for (int f = 0; f < 8; ++f) ra[f] = fz_ld_h8(rs + (12 + f) * 16);      // passes 2, 3: tiles 6..9 = fragments 12..19
             fz_wait_vm0();                                                          // sub-step 3
 #pragma unroll
-            for (int f = 0; f < 8; ++f) asm volatile("" : "+v"(ra[f]));
+            for (int f = 0; f < 8; ++f) FZ_PIN_V(ra[f]);
             fz_barrier_nodrain();
             if (step + 2 < NSTEP) issue_step(step + 2);
             ++step;

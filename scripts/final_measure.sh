@@ -8,9 +8,9 @@ else
   (timeout 1700 python -m pytest tests -x -q -s -m gpu) > $O/gpu_tests.log 2>&1
 fi
 tail -2 $O/gpu_tests.log
-(timeout 500 python bench.py --steps 5 --warmup 2 $BENCH_EXTRA) > $O/bench.json 2> $O/bench.err; head -c 400 $O/bench.json; echo
+(timeout 500 python bench.py --full --steps 5 --warmup 2 $BENCH_EXTRA) > $O/bench.json 2> $O/bench.err; head -c 400 $O/bench.json; echo
 cd /tmp; export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe > $O/bench_prof.json 2> $O/bench_prof.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe > $O/bench_prof.json 2> $O/bench_prof.err
 cd $R
 f=$(ls $O/prof/*/bench_kernel_stats.csv $O/prof/bench_kernel_stats.csv 2>/dev/null | head -1)
 cp "$f" $O/kernel_stats.csv 2>/dev/null; head -5 $O/kernel_stats.csv | cut -c1-120

@@ -8,9 +8,9 @@ tail -16 $O/gpu_tests.log
 rm -f $R/build_tmp/flash_ab
 bash scripts/pmc_flash.sh 1 flash_d40_final2 > /dev/null 2>&1; cp $R/gpurun_out/pmc/flash_d40_final2.json $O/pmc_flash_d40_final2.json 2>/dev/null
 cp $O/pmc_flash_d40_final2.json $R/profiles/r03_pmc_flash_d40_final2.json 2>/dev/null   # the bench line's `traffic` reads it
-(timeout 300 python bench.py --steps 5 --warmup 2) > $O/bench.json 2> $O/bench.err; head -c 300 $O/bench.json; echo
+(timeout 300 python bench.py --full --steps 5 --warmup 2) > $O/bench.json 2> $O/bench.err; head -c 300 $O/bench.json; echo
 cd /tmp; export TMPDIR=/tmp
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe > $O/bench_prof.json 2> $O/bench_prof.err
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe > $O/bench_prof.json 2> $O/bench_prof.err
 cd $R
 f=$(ls $O/prof/*/bench_kernel_stats.csv $O/prof/bench_kernel_stats.csv 2>/dev/null | head -1)
 cp "$f" $O/kernel_stats.csv 2>/dev/null; head -4 $O/kernel_stats.csv | cut -c1-120

@@ -8,8 +8,8 @@ if [ "$SWEEP" != "0" ]; then
 (timeout 300 python scripts/kbench.py --conv) > $O/kbench_conv.json 2> $O/kbench_conv.err
 fi
 cd /tmp; export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --full --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err
 cd $R
 f=$(ls $O/prof/*/bench_kernel_stats.csv $O/prof/bench_kernel_stats.csv 2>/dev/null | head -1); cp "$f" $O/kernel_stats.csv; rm -rf $O/prof
-if [ "$PLAIN" = "1" ]; then (timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline) > $O/bench.json 2> $O/bench.err; fi
+if [ "$PLAIN" = "1" ]; then (timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline) > $O/bench.json 2> $O/bench.err; fi
 head -c 600 $O/bench_prof.json; echo; tail -2 $O/bench_prof.err

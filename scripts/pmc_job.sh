@@ -7,7 +7,7 @@ TAG=${1:-pmc_job}; T=${2:-50}; EXTRA="${@:3}"; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun
 cd /tmp; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   FZ_BENCH_LAUNCHLOG=$OUT/launchlog_$c.json timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o p -- \
-    python $R/bench.py --steps 1 --warmup 0 --ddim-steps $T --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe --no-box $EXTRA > $OUT/$c.log 2>&1
+    python $R/bench.py --full --steps 1 --warmup 0 --ddim-steps $T --no-cpu-baseline --no-kernel-breakdown --no-n-edit2-probe --no-box $EXTRA > $OUT/$c.log 2>&1
   tail -2 $OUT/$c.log
 done
 python $R/scripts/pmc_job_summary.py $OUT $R/gpurun_out/$TAG.json $T

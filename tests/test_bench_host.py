@@ -123,7 +123,7 @@ def _run_bench_ranks(world, extra, timeout=600):
 
 def test_bench_main_two_ranks_clips_and_frame_shard_probe():
     """Default sharding (one clip per rank, weak scaling) + the frame-sharded probe that follows it, end to end over gloo."""
-    line = _run_bench_ranks(2, ["--no-kernel-breakdown", "--transport", "rccl"])  # (the per-kernel event brackets are single-rank bookkeeping: test_rooflines_bookkeeping)
+    line = _run_bench_ranks(2, ["--full", "--no-kernel-breakdown", "--transport", "rccl"])  # (the per-kernel event brackets are single-rank bookkeeping: test_rooflines_bookkeeping)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["n_ranks_seen"] == 2
     assert line["config"]["parallelism"] == "dp2 over clips" and line["config"]["outputs_finite"] is True
     assert line["value"] > 0 and abs(line["value"] - 2 * 2 * 1 / (line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]  # whole-job frames/s
@@ -212,7 +212,7 @@ def test_bench_main_single_rank_with_the_kernel_breakdown_job():
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_cpu_harness.py"), "--steps", "1", "--warmup", "0", "--ddim-steps", "2",
-           "--frames", "2", "--latent-size", "8", "--no-cpu-baseline", "--split-steps", "2", "--split-iters", "3"]   # (the bisection: 3 short jobs, not 10)
+           "--frames", "2", "--latent-size", "8", "--no-cpu-baseline", "--split-steps", "2", "--split-iters", "3", "--full"]   # (the bisection: 3 short jobs, not 10)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, check=True, timeout=600, capture_output=True, text=True, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -220,6 +220,36 @@ def test_bench_main_single_rank_with_the_kernel_breakdown_job():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["value"] > 0 and isinstance(line["rooflines"], list) and line["config"]["outputs_finite"] is True
     assert line["config_faithful_n_edit_2"]["outputs_finite"] is True
+
+
+def test_bench_main_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """Without --full the run is setup, warm-up, the K timed jobs and the line; --dump-outputs writes the last timed job's edited latents,
+    and two runs with the same arguments write the same numbers (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_cpu_harness.py"), "--steps", "2", "--warmup", "1", "--ddim-steps", "2",
+               "--frames", "2", "--latent-size", "8", "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, check=True, timeout=600, capture_output=True, text=True, env=env)
+        got = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, out.stdout + out.stderr
+        lines.append(json.loads(got[0]))
+        dumps.append(np.load(tmp_path / run / "edited_latents.npy"))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step_spread"]["jobs"] == 2 and line["config"]["outputs_finite"] is True
+    assert abs(line["value"] - 2 / (line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]
+    assert line["roofline"] is None and line["rooflines"] is None and line["cpu_baseline"] is None
+    for k in ("box", "value_normalised", "config_faithful_n_edit_2", "split_mask_job", "frame_sharded"):
+        assert k not in line, k
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (1, 4, 2, 8, 8) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
 
 
 def test_inject_timer_prices_the_rows_really_read():

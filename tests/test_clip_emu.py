@@ -78,29 +78,15 @@ def test_tokenize_layout(tmp_path):
     assert cut[-1] == eot and int((cut != 0).sum()) == 77
 
 
-REF_BPE = "/root/reference/CLIP/clip/bpe_simple_vocab_16e6.txt.gz"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_BPE), reason="the reference tree only exists in the authoring container")
 def test_tokenize_equals_the_reference_tokenizer():
-    """Same ids as the reference's SimpleTokenizer (clip/simple_tokenizer.py, imported by file path with a pass-through ftfy stub --
-    ftfy is not installed here and only repairs mojibake) on the metric's prompts and some awkward ones."""
-    import importlib.util
-    import sys
-    import types
+    """Same ids as the reference's SimpleTokenizer (clip/simple_tokenizer.py) on the metric's prompts and some awkward ones: the ids it
+    returned are recorded, with its merges file reduced to the merges these prompts reach, at their ranks (oracle/gen_golden_tokenizer.py)."""
+    import json
     from fatezero_amd import clip
-    sys.modules.setdefault("ftfy", types.SimpleNamespace(fix_text=lambda s: s))
-    spec = importlib.util.spec_from_file_location("ref_simple_tokenizer", "/root/reference/CLIP/clip/simple_tokenizer.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    ref = mod.SimpleTokenizer(REF_BPE)
-    sot, eot = ref.encoder["<|startoftext|>"], ref.encoder["<|endoftext|>"]
-    prompts = ["a silver jeep driving down a curvy road in the countryside", "a Porsche car driving down a curvy road in the countryside",
-               "watercolor painting of a silver jeep driving down a curvy road", "A squirrel, eating a carrot!", "van gogh style: rabbit's jump",
-               "  two   spaces\tand tabs ", "swarovski crystal swan swimming in a river near a wall and bushes", "3 cats & 12 tigers (cartoon)"]
-    got = clip.tokenize(prompts, bpe_path=REF_BPE)
-    for p, row in zip(prompts, got):
-        want = [sot] + ref.encode(p) + [eot]
+    gold = json.load(open(os.path.join(CC.GOLD, "clip_tokenizer_ids.json")))
+    got = clip.tokenize(gold["prompts"], bpe_path=os.path.join(CC.GOLD, "clip_bpe_prompts.txt.gz"))
+    for p, row, want in zip(gold["prompts"], got, gold["ids"]):
+        assert want[0] == gold["sot"] and want[-1] == gold["eot"]
         assert row[:len(want)].tolist() == want and bool((row[len(want):] == 0).all()), p
 
 
