@@ -520,7 +520,10 @@ int fz_attn_flash_dispatch(const FzAttnSelfDesc& d, const void* q, const void* k
                 return big ? launch_flash<40, 2, 2, false>(d, q, k, vt, o, stream)
                            : launch_flash<40, 4, 1, false>(d, q, k, vt, o, stream);
             return big ? launch_flash<40, 2, 2>(d, q, k, vt, o, stream) : launch_flash<40, 4, 1>(d, q, k, vt, o, stream);
-        case 64: return launch_flash<64, 2, 1>(d, q, k, vt, o, stream);
+        case 64:  // SD-2.x (64-wide heads at every level).  The two-query-block form <64, 2, 2> fills all 256 VGPRs of two waves per SIMD
+                  // and spills; the same-process A/B at SD-2's shapes (profiles/r07_flash_d64_ab.txt, scripts/flash_ab_d64.hip) has it 14 %
+                  // slower at 8 x 5 heads x lq 4096, equal at 16 frames and 16-24 % slower at 10 heads x lq 1024 -- one form at every lq
+            return launch_flash<64, 2, 1>(d, q, k, vt, o, stream);
         case 80: return launch_flash<80, 2, 1>(d, q, k, vt, o, stream);
         case 128: return launch_flash<128, 1, 1>(d, q, k, vt, o, stream);
         case 160: return launch_flash<160, 1, 1>(d, q, k, vt, o, stream);

@@ -121,7 +121,12 @@ def layer_norm_tokens(norm, x):
 
 class CrossAttention(nn.Module):
     """Parameter container + executor for diffusers' CrossAttention as used by the reference (to_q/to_k/to_v without
-    bias, to_out = [Linear, Dropout]); head count = `heads`, scale = dim_head**-0.5."""
+    bias, to_out = [Linear, Dropout]); head count = `heads`, scale = dim_head**-0.5.
+
+    `upcast_attention` (SD-2.x configs) needs no separate path: the reference's upcast (attention_register.py:24) forms
+    scale * Q K^T from fp32 copies of fp16 q / k and takes the softmax in fp32.  Every attention kernel here already does exactly
+    that -- the products of fp16 q / k elements are exact in the fp32 MFMA accumulators and the softmax runs in fp32 -- so both
+    settings run the same kernels (tests/test_sd2_emu.py pins the upcast golden recorded from the reference)."""
 
     def __init__(self, query_dim, cross_attention_dim=None, heads=8, dim_head=64, dropout=0.0, bias=False,
                  upcast_attention=False, **unused):
@@ -572,19 +577,25 @@ class SpatioTemporalTransformerBlock(nn.Module):
 
 
 class SpatioTemporalTransformerModel(nn.Module):
-    """attention.py:31-144: per-frame GroupNorm(eps 1e-6) -> 1x1 proj_in -> block -> 1x1 proj_out -> + residual."""
+    """attention.py:31-144: per-frame GroupNorm(eps 1e-6) -> 1x1 proj_in -> block -> 1x1 proj_out -> + residual.
+
+    use_linear_projection (SD-2.x, attention.py:63-66,90-93): proj_in / proj_out are Linear layers applied after / before the
+    '(h w) c' rearrange instead of 1x1 convolutions in front of / behind it.  On token-major activations both forms are the same GEMM;
+    only the parameter shape differs ([C, C] instead of [C, C, 1, 1]), so the state_dict keys and shapes stay the reference's."""
 
     def __init__(self, num_attention_heads=16, attention_head_dim=88, in_channels=None, num_layers=1,
-                 norm_num_groups=32, cross_attention_dim=None, model_config: dict = {}, **unused):
+                 norm_num_groups=32, cross_attention_dim=None, model_config: dict = {}, use_linear_projection=False, **unused):
         super().__init__()
         assert num_layers == 1
         inner = num_attention_heads * attention_head_dim
+        self.use_linear_projection = use_linear_projection
         self.norm = _NormParams(in_channels, norm_num_groups, 1e-6)
-        self.proj_in = _Conv1x1Params(in_channels, inner)
+        self.proj_in = _Conv1x1Params(in_channels, inner, linear=use_linear_projection)
         self.transformer_blocks = nn.ModuleList([SpatioTemporalTransformerBlock(
             inner, num_attention_heads, attention_head_dim, cross_attention_dim=cross_attention_dim,
             model_config=model_config)])
-        self.proj_out = _Conv1x1Params(inner, in_channels)
+        # (the reference builds the linear proj_out as nn.Linear(in_channels, inner_dim): the same [C, C] weight, inner == in_channels)
+        self.proj_out = _Conv1x1Params(inner, in_channels, linear=use_linear_projection)
 
     def forward_tokens(self, x: Tokens, ctx) -> Tokens:
         h = group_norm_tokens(self.norm, x, span_frames=False, silu=False)
@@ -609,11 +620,12 @@ class SpatioTemporalTransformerModel(nn.Module):
 
 
 class _Conv1x1Params(nn.Module):
-    """nn.Conv2d(k=1) parameters ([Cout, Cin, 1, 1]) applied as a GEMM on token-major data."""
+    """nn.Conv2d(k=1) parameters ([Cout, Cin, 1, 1]) -- or, `linear`, nn.Linear parameters ([Cout, Cin]) -- applied as a GEMM on
+    token-major data."""
 
-    def __init__(self, cin, cout):
+    def __init__(self, cin, cout, linear=False):
         super().__init__()
-        self.weight = nn.Parameter(torch.empty(cout, cin, 1, 1))
+        self.weight = nn.Parameter(torch.empty((cout, cin) if linear else (cout, cin, 1, 1)))
         nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)
         self.bias = nn.Parameter(torch.zeros(cout))
         self._packed = None

@@ -255,8 +255,12 @@ class CLIPTokenizer:
     def from_pretrained(cls, pretrained_model_path, subfolder=None, **unused):
         root = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
         kw = {}
-        cfg = os.path.join(root, "tokenizer_config.json")
-        if os.path.exists(cfg):
+        # special_tokens_map.json first, tokenizer_config.json over it (transformers' order).  SD-2.x's OpenCLIP tokenizer pads with "!"
+        # (id 0) instead of SD-1.x's <|endoftext|>, stated in both files.
+        for name in ("special_tokens_map.json", "tokenizer_config.json"):
+            cfg = os.path.join(root, name)
+            if not os.path.exists(cfg):
+                continue
             with open(cfg) as f:
                 tc = json.load(f)
             for key in ("bos_token", "eos_token", "pad_token"):

@@ -12,10 +12,11 @@ def _resnet(cin, cout, temb, eps, groups, scale, mc):
                                output_scale_factor=scale, model_config=mc)
 
 
-def _transformer(heads, channels, cross_dim, groups, mc):
+def _transformer(heads, channels, cross_dim, groups, mc, linear=False):
     # attn_num_head_channels is used as the head COUNT, dim_head = channels // heads (unet_3d_blocks.py:269-272)
     return SpatioTemporalTransformerModel(heads, channels // heads, in_channels=channels, num_layers=1,
-                                          cross_attention_dim=cross_dim, norm_num_groups=groups, model_config=mc)
+                                          cross_attention_dim=cross_dim, norm_num_groups=groups, model_config=mc,
+                                          use_linear_projection=linear)
 
 
 class CrossAttnDownBlockPseudo3D(nn.Module):
@@ -23,13 +24,13 @@ class CrossAttnDownBlockPseudo3D(nn.Module):
 
     def __init__(self, in_channels, out_channels, temb_channels, num_layers=1, resnet_eps=1e-6, resnet_groups=32,
                  attn_num_head_channels=1, cross_attention_dim=1280, output_scale_factor=1.0, add_downsample=True,
-                 model_config: dict = {}, **unused):
+                 model_config: dict = {}, use_linear_projection=False, **unused):
         super().__init__()
         self.resnets = nn.ModuleList([_resnet(in_channels if i == 0 else out_channels, out_channels, temb_channels,
                                               resnet_eps, resnet_groups, output_scale_factor, model_config)
                                       for i in range(num_layers)])
         self.attentions = nn.ModuleList([_transformer(attn_num_head_channels, out_channels, cross_attention_dim,
-                                                      resnet_groups, model_config) for _ in range(num_layers)])
+                                                      resnet_groups, model_config, use_linear_projection) for _ in range(num_layers)])
         self.downsamplers = None
         if add_downsample:
             self.downsamplers = nn.ModuleList([DownsamplePseudo3D(out_channels, use_conv=True, out_channels=out_channels,
@@ -75,12 +76,13 @@ class UNetMidBlockPseudo3DCrossAttn(nn.Module):
     has_cross_attention = True
 
     def __init__(self, in_channels, temb_channels, resnet_eps=1e-6, resnet_groups=32, attn_num_head_channels=1,
-                 output_scale_factor=1.0, cross_attention_dim=1280, model_config: dict = {}, **unused):
+                 output_scale_factor=1.0, cross_attention_dim=1280, model_config: dict = {},
+                 use_linear_projection=False, **unused):
         super().__init__()
         self.resnets = nn.ModuleList([_resnet(in_channels, in_channels, temb_channels, resnet_eps, resnet_groups,
                                               output_scale_factor, model_config) for _ in range(2)])
         self.attentions = nn.ModuleList([_transformer(attn_num_head_channels, in_channels, cross_attention_dim,
-                                                      resnet_groups, model_config)])
+                                                      resnet_groups, model_config, use_linear_projection)])
 
     def forward_tokens(self, x: Tokens, temb_act, ctx):
         x = self.resnets[0].forward_tokens(x, temb_act)
@@ -97,7 +99,7 @@ class CrossAttnUpBlockPseudo3D(nn.Module):
 
     def __init__(self, in_channels, out_channels, prev_output_channel, temb_channels, num_layers=1, resnet_eps=1e-6,
                  resnet_groups=32, attn_num_head_channels=1, cross_attention_dim=1280, output_scale_factor=1.0,
-                 add_upsample=True, model_config: dict = {}, **unused):
+                 add_upsample=True, model_config: dict = {}, use_linear_projection=False, **unused):
         super().__init__()
         res = []
         for i in range(num_layers):
@@ -107,7 +109,7 @@ class CrossAttnUpBlockPseudo3D(nn.Module):
                                model_config))
         self.resnets = nn.ModuleList(res)
         self.attentions = nn.ModuleList([_transformer(attn_num_head_channels, out_channels, cross_attention_dim,
-                                                      resnet_groups, model_config) for _ in range(num_layers)])
+                                                      resnet_groups, model_config, use_linear_projection) for _ in range(num_layers)])
         self.upsamplers = None
         if add_upsample:
             self.upsamplers = nn.ModuleList([UpsamplePseudo3D(out_channels, use_conv=True, out_channels=out_channels,

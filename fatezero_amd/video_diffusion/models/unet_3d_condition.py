@@ -35,6 +35,38 @@ class _TimestepEmbedding(nn.Module):
         self.linear_2 = _LinearParams(cout, cout)
 
 
+# Keys that newer diffusers versions write into a 2-D UNet's config.json (SD-2.x checkpoints re-saved with them included).  Each is
+# accepted at the value that means "the architecture the reference builds"; any other value is refused by name.
+_NEWER_KEY_DEFAULTS = {
+    "time_embedding_type": "positional", "conv_in_kernel": 3, "conv_out_kernel": 3, "transformer_layers_per_block": 1,
+    "reverse_transformer_layers_per_block": None, "encoder_hid_dim": None, "encoder_hid_dim_type": None,
+    "addition_embed_type": None, "addition_time_embed_dim": None, "addition_embed_type_num_heads": 64,
+    "time_embedding_dim": None, "time_embedding_act_fn": None, "timestep_post_act": None, "time_cond_proj_dim": None,
+    "projection_class_embeddings_input_dim": None, "class_embeddings_concat": False, "mid_block_only_cross_attention": None,
+    "cross_attention_norm": None, "resnet_skip_time_act": False, "resnet_out_scale_factor": 1.0, "attention_type": "default",
+    "dropout": 0.0,
+}
+
+
+def _check_newer_keys(kwargs, attention_head_dim):
+    """Removes the newer-diffusers keys from `kwargs` after checking each holds its default (what remains is model_config)."""
+    rest = dict(kwargs)
+    for key, default in _NEWER_KEY_DEFAULTS.items():
+        if key not in rest:
+            continue
+        v = rest.pop(key)
+        ok = v == default or (key == "transformer_layers_per_block" and isinstance(v, (list, tuple)) and all(x == 1 for x in v))
+        if not ok:
+            raise NotImplementedError(f"UNet config {key}={v!r} is not supported (only {default!r}, the reference's architecture)")
+    if "num_attention_heads" in rest:  # newer diffusers: the head COUNT under its proper name; None = attention_head_dim is the count
+        v = rest.pop("num_attention_heads")
+        if v is not None and v != attention_head_dim and list(v if isinstance(v, (list, tuple)) else [v]) != list(
+                attention_head_dim if isinstance(attention_head_dim, (list, tuple)) else [attention_head_dim]):
+            raise NotImplementedError(f"UNet config num_attention_heads={v!r} differs from attention_head_dim={attention_head_dim!r}: "
+                                      "the reference takes the head count from attention_head_dim")
+    return rest
+
+
 TIME_EMBED_CACHE = True  # (switch for same-box A/B runs: False = the timestep enters as a device tensor at every forward, as before)
 
 
@@ -53,15 +85,19 @@ class UNetPseudo3DConditionModel(nn.Module):
                  use_linear_projection: bool = False, class_embed_type=None, num_class_embeds=None,
                  upcast_attention: bool = False, resnet_time_scale_shift: str = "default", **kwargs):
         super().__init__()
-        if (center_input_sample or not flip_sin_to_cos or freq_shift != 0 or dual_cross_attention or use_linear_projection
+        if (center_input_sample or not flip_sin_to_cos or freq_shift != 0 or dual_cross_attention
                 or class_embed_type is not None or num_class_embeds is not None or resnet_time_scale_shift != "default"
                 or act_fn not in ("silu", "swish") or kwargs.get("temporal_downsample") or kwargs.get("temporal_downsample_time", 0)):
-            raise NotImplementedError("only the SD-1.x configuration surface used by FateZero is implemented")
+            raise NotImplementedError("only the SD-1.x / SD-2.x configuration surface used by FateZero is implemented")
+        kwargs = _check_newer_keys(kwargs, attention_head_dim)
+        # SD-2.x: use_linear_projection (Linear proj_in / proj_out), per-level head counts, a 1024-wide context.  upcast_attention
+        # is accepted as is: the attention kernels already take QK^T and the softmax in fp32 (attention.py: CrossAttention).
         cfg = dict(sample_size=sample_size, in_channels=in_channels, out_channels=out_channels,
                    down_block_types=tuple(down_block_types), up_block_types=tuple(up_block_types),
                    block_out_channels=tuple(block_out_channels), layers_per_block=layers_per_block,
                    norm_num_groups=norm_num_groups, norm_eps=norm_eps, cross_attention_dim=cross_attention_dim,
-                   attention_head_dim=attention_head_dim, center_input_sample=False, **kwargs)
+                   attention_head_dim=attention_head_dim, center_input_sample=False,
+                   use_linear_projection=bool(use_linear_projection), upcast_attention=bool(upcast_attention), **kwargs)
         self.config = SimpleNamespace(**cfg)
         self.sample_size = sample_size
         model_config = dict(kwargs)
@@ -79,15 +115,18 @@ class UNetPseudo3DConditionModel(nn.Module):
                 t, num_layers=layers_per_block, in_channels=in_c, out_channels=out_c, temb_channels=time_embed_dim,
                 add_downsample=not final, resnet_eps=norm_eps, resnet_groups=norm_num_groups,
                 cross_attention_dim=cross_attention_dim, attn_num_head_channels=attention_head_dim[i],
-                model_config=model_config))
+                model_config=model_config, use_linear_projection=use_linear_projection))
         # the reference ignores `mid_block_type` (unet_3d_condition.py:167-181 always builds the cross-attention mid block), so a
         # 2-D config.json of a newer diffusers ("UNetMidBlock2DCrossAttn") loads there -- and here
-        if only_cross_attention not in (False, None) or downsample_padding != 1:
-            raise NotImplementedError("only_cross_attention / downsample_padding != 1 are not used by any SD-1.x checkpoint")
+        if any(only_cross_attention) if isinstance(only_cross_attention, (list, tuple)) else only_cross_attention not in (False, None):
+            raise NotImplementedError("only_cross_attention is not used by any SD-1.x / SD-2.x checkpoint")
+        if downsample_padding != 1:
+            raise NotImplementedError("downsample_padding != 1 is not used by any SD-1.x / SD-2.x checkpoint")
         self.mid_block = UNetMidBlockPseudo3DCrossAttn(
             in_channels=block_out_channels[-1], temb_channels=time_embed_dim, resnet_eps=norm_eps,
             output_scale_factor=mid_block_scale_factor, cross_attention_dim=cross_attention_dim,
-            attn_num_head_channels=attention_head_dim[-1], resnet_groups=norm_num_groups, model_config=model_config)
+            attn_num_head_channels=attention_head_dim[-1], resnet_groups=norm_num_groups, model_config=model_config,
+            use_linear_projection=use_linear_projection)
         self.up_blocks = nn.ModuleList()
         rev_c = list(reversed(block_out_channels))
         rev_h = list(reversed(attention_head_dim))
@@ -102,7 +141,8 @@ class UNetPseudo3DConditionModel(nn.Module):
             self.up_blocks.append(get_up_block(
                 t, num_layers=layers_per_block + 1, in_channels=in_c, out_channels=out_c, prev_output_channel=prev,
                 temb_channels=time_embed_dim, add_upsample=not final, resnet_eps=norm_eps, resnet_groups=norm_num_groups,
-                cross_attention_dim=cross_attention_dim, attn_num_head_channels=rev_h[i], model_config=model_config))
+                cross_attention_dim=cross_attention_dim, attn_num_head_channels=rev_h[i], model_config=model_config,
+                use_linear_projection=use_linear_projection))
         self.conv_norm_out = _NormParams(block_out_channels[0], norm_num_groups, norm_eps)
         self.conv_out = PseudoConv3d(block_out_channels[0], out_channels, kernel_size=3, padding=1, model_config=model_config)
         self._issuer = None  # fatezero_amd.issue.IssuePlans once enable_issue_plans() was called

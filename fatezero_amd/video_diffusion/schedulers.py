@@ -9,6 +9,12 @@ import numpy as np
 import torch
 
 
+# Scheduler-config keys of newer diffusers versions (SD-2.x-base's scheduler_config.json re-saved with them) and the values that
+# leave the DDIM arithmetic of diffusers 0.11.1 unchanged (dynamic_thresholding_ratio / sample_max_value / clip_sample_range only act
+# under thresholding / clip_sample, both refused, and are ignored).
+_NEWER_KEY_DEFAULTS = {"timestep_spacing": "leading", "thresholding": False, "rescale_betas_zero_snr": False, "trained_betas": None}
+
+
 class DDIMScheduler:
     order = 1
 
@@ -20,7 +26,12 @@ class DDIMScheduler:
             betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
         else:
             raise NotImplementedError(beta_schedule)
-        if prediction_type != "epsilon" or clip_sample:
+        if prediction_type != "epsilon":
+            # (SD-2.x 768-v checkpoints.)  The reference's inversion step treats the UNet output as epsilon whatever the config says
+            # (p2p_ddim_spatial_temporal.py:150-161, next_clean2noise_step), so there is no reference behaviour to be a drop-in for
+            raise NotImplementedError(f"prediction_type={prediction_type!r}: FateZero's DDIM inversion treats the UNet output as "
+                                      "epsilon, so only epsilon-prediction checkpoints (SD-1.x, SD-2.x-base) are supported")
+        if clip_sample:
             raise NotImplementedError("FateZero runs epsilon prediction without sample clipping")
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, clip_sample=False, set_alpha_to_one=set_alpha_to_one,
@@ -42,6 +53,9 @@ class DDIMScheduler:
         kw = {k: config[k] for k in keys if k in config}
         # clip_sample / steps_offset are forced by the pipeline anyway (stable_diffusion.py:56-81); PNDM-style configs of the
         # SD checkpoints carry `skip_prk_steps` etc., which DDIM ignores like diffusers' from_config does
+        for key, default in _NEWER_KEY_DEFAULTS.items():  # newer diffusers write these: only their defaults describe this scheduler
+            if key in config and config[key] != default:
+                raise NotImplementedError(f"scheduler config {key}={config[key]!r} is not supported (only {default!r})")
         return cls(**kw)
 
     @classmethod
