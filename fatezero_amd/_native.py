@@ -15,6 +15,7 @@ FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = 0, 1, 2
 FZ_MAX_KV_SLOTS = 4
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80
+FZ_TEMPORAL_MAX_FRAMES = 256
 
 
 class FzAttnSelfDesc(C.Structure):

@@ -1,7 +1,8 @@
 // attn_temporal.hip -- temporal attention over the F frames of every (batch, pixel, head): the un-patched
 // diffusers CrossAttention.forward applied on '(b d) f c' (attention.py:327-337 of the reference).
 //
-// The sequence length is the clip length (8..32), so this is a bandwidth problem, not an MFMA one: q, k, v stay
+// Up to 64 frames the sequence length is the clip length (8..32 in the reference's configs), so this is a bandwidth problem, not an
+// MFMA one (longer clips, up to FZ_TEMPORAL_MAX_FRAMES, take attn_temporal_long_kernel further down, which is an MFMA one): q, k, v stay
 // in their native token-major layout [(b f)][token][channel] (no '(b f) d c -> (b d) f c' rearrange is ever
 // materialised); one thread owns one (token, head, query frame), the F key/value rows of its pixel are shared
 // through L1 by the F threads of that pixel, and scores live in LDS.
@@ -9,7 +10,8 @@
 #include "../../include/fatezero_hip.h"
 #include <stdlib.h>
 
-#define TMAXF 64
+#define TMAXF 64                                 // the one-thread-per-query-frame kernels below serve clips up to here ...
+#define TLONG_MAXF FZ_TEMPORAL_MAX_FRAMES        // ... attn_temporal_long_kernel (matrix pipe) the longer ones
 #define TTHREADS 256
 
 struct TemporalArgs {
@@ -222,13 +224,194 @@ FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_lds_kernel(TemporalArgs
     }
 }
 
+// Long clips (kv_frames or q_frames > 64): per (token, head) this is a small dense attention, F x F x d, and the F^2 work of the
+// one-thread-per-query-frame kernels above would sit on the vector ALUs -- so both products go to the matrix pipe
+// (v_mfma_f32_32x32x16_f16) in the TRANSPOSED form, which needs no register transpose between them:
+//   S^T = K Q^T   A = K tile [32 keys][16 ch], B = Q^T [16 ch][32 queries]: both fragments are 16 contiguous bytes of a global row.
+//                 C: lane (i, hi) holds, for query i, keys 32t + 8g + 4hi + r of tile t in register 4g + r (g, r = 0..3).
+//   softmax       over the keys of a query = over the lane's NT x 16 registers and the lane pair (l, l ^ 32).  The WHOLE row is in
+//                 registers (NT <= 8 tiles x 16 fp32), so it is the exact two-pass softmax of the reference: P is normalised, THEN
+//                 rounded to fp16, then multiplied -- an online softmax could only round the un-normalised P.  That register file of
+//                 scores is what sets FZ_TEMPORAL_MAX_FRAMES = 8 x 32.
+//   O^T = V^T P^T B = P^T [16 keys][32 queries] is the C fragment above as it lies (registers 8kc..8kc+7 of tile t -> half8), i.e.
+//                 contraction slot (kc, hi, e) of tile t is key 32t + 16kc + 8(e >> 2) + 4hi + (e & 3): bits 2 and 3 of the key's
+//                 offset inside its group of 16 are swapped against the natural order.  A = V^T [32 ch][16 keys] has to supply
+//                 the same keys in the same slots: V is staged once per workgroup into LDS TRANSPOSED, Vt[head][ch][key position],
+//                 with that swap applied to the position, so an A fragment is one 16-byte LDS read.
+//                 C: lane (i, hi) holds, for query i, channels 32ct + 8g + 4hi + r: four 8-byte stores per channel tile.
+// One workgroup = one (batch element, token, group of `hg` heads); its 4 waves share the staged V and split the (head, 32-query
+// tile) items.  Frames beyond the clip (F % 32 != 0) and channels beyond head_dim (head_dim % 32 != 0) are never read: their
+// fragments are zero, the scores of padded keys are masked before the softmax, and the padded key positions of Vt are zero-filled
+// (P is exactly 0 there; 0 x stale LDS could still be NaN).
+struct TemporalLongArgs {
+    const half_t *q, *k, *v;
+    half_t* o;
+    int F, Fq, tokens, heads, dh;
+    int hg, ngroups, ldv;  // heads per workgroup, workgroups per token, halves between channel rows of Vt (32 NT + 8)
+    int64_t in_stride, q_stride, out_stride;
+    float scale;
+};
+
+FZ_DEVICE int tlong_key_pos(int key) { return (key & ~12) | ((key & 4) << 1) | ((key & 8) >> 1); }
+
+template <int NT>
+FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_long_kernel(TemporalLongArgs a) {
+    FZ_DYN_SMEM(raw);
+    half_t* Vt = reinterpret_cast<half_t*>(raw);  // [hg][dh][ldv]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y;
+    const int tok = blockIdx.x / a.ngroups;
+    const int h0 = (blockIdx.x % a.ngroups) * a.hg;
+    const int F = a.F, dh = a.dh, ldv = a.ldv;
+    const int nvec = dh >> 3;
+    // ---- stage V of the group's heads, transposed: lanes walk the keys (adjacent 2-byte LDS columns), then chunks, then heads
+    for (int id = tid; id < a.hg * nvec * (NT * 32); id += TTHREADS) {
+        const int key = id % (NT * 32), cv = (id / (NT * 32)) % nvec, hl = id / (NT * 32 * nvec);
+        half8_t vv = fz_zero_h8();
+        if (key < F) vv = fz_ld_h8(a.v + ((int64_t)(b * F + key) * a.tokens + tok) * a.in_stride + (h0 + hl) * dh + cv * 8);
+        half_t* dst = Vt + ((size_t)hl * dh + cv * 8) * ldv + tlong_key_pos(key);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dst[(size_t)e * ldv] = vv[e];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = fz_uniform(tid >> 6);
+    const int i = lane & 31, hi = lane >> 5;
+    const int nq = (a.Fq + 31) >> 5;
+    const int64_t kv_frame = (int64_t)a.tokens * a.in_stride;  // halves between the same token of consecutive frames
+    for (int item = wave; item < a.hg * nq; item += TTHREADS / 64) {
+        const int hl = item / nq, qt = item % nq;
+        const int col = (h0 + hl) * dh;
+        const int qf = qt * 32 + i;
+        const bool qok = qf < a.Fq;
+        const half_t* qrow = a.q + ((int64_t)(b * a.Fq + (qok ? qf : 0)) * a.tokens + tok) * a.q_stride + col;
+        const half_t* krow = a.k + ((int64_t)b * F * a.tokens + tok) * a.in_stride + col;  // frame 0 of this batch element
+        // ---- S^T = K Q^T
+        f32x16 s[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) s[t] = fz_zero_f16v();
+        for (int c0 = 0; c0 < dh; c0 += 16) {
+            const int ch = c0 + 8 * hi;
+            const bool chok = ch < dh;
+            const half8_t qfrag = (qok && chok) ? fz_ld_h8(qrow + ch) : fz_zero_h8();
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int key = 32 * t + i;
+                const half8_t kfrag = (key < F && chok) ? fz_ld_h8(krow + key * kv_frame + ch) : fz_zero_h8();
+                s[t] = fz_mfma_32x32x16_f16(kfrag, qfrag, s[t]);
+            }
+        }
+        // ---- exact softmax over the keys of query i
+        float mx = -1e30f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = 32 * t + 8 * (r >> 2) + 4 * hi + (r & 3);
+                const float x = key < F ? s[t][r] * a.scale : -1e30f;
+                s[t][r] = x;
+                mx = fmaxf(mx, x);
+            }
+        mx = fz_pair_max32(mx);
+        float sum = 0.0f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = 32 * t + 8 * (r >> 2) + 4 * hi + (r & 3);
+                const float e = key < F ? __builtin_expf(s[t][r] - mx) : 0.0f;
+                s[t][r] = e;
+                sum += e;
+            }
+        sum += fz_shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        half8_t p[NT][2];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) p[t][r >> 3][r & 7] = (half_t)(s[t][r] * inv);  // P is cast to fp16 before P.V
+        // ---- O^T = V^T P^T, one 32-channel tile at a time
+        const half_t* vh = Vt + (size_t)hl * dh * ldv;
+        half_t* orow = a.o + ((int64_t)(b * a.Fq + (qok ? qf : 0)) * a.tokens + tok) * a.out_stride + col;
+        for (int c0 = 0; c0 < dh; c0 += 32) {
+            const bool chok = c0 + i < dh;
+            const half_t* vrow = vh + (size_t)(chok ? c0 + i : 0) * ldv + 8 * hi;
+            f32x16 acc = fz_zero_f16v();
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int kc = 0; kc < 2; ++kc) {
+                    const half8_t vfrag = chok ? fz_ld_h8(vrow + 32 * t + 16 * kc) : fz_zero_h8();
+                    acc = fz_mfma_32x32x16_f16(vfrag, p[t][kc], acc);
+                }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ch = c0 + 8 * g + 4 * hi;
+                if (qok && ch < dh) {
+                    half4_t ov;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ov[r] = (half_t)acc[4 * g + r];
+                    *reinterpret_cast<half4_t*>(orow + ch) = ov;
+                }
+            }
+        }
+    }
+}
+
+// heads per workgroup of the long-clip kernel: the largest divisor of `heads` whose transposed V fits 64 KB (two workgroups per CU and
+// no opt-in attribute); a single head beyond that (head_dim 160 from 193 frames) takes the opt-in path, 84.5 KB at the very most
+static int tlong_launch(const TemporalLongArgs& a0, int batch, void* stream) {
+    TemporalLongArgs a = a0;
+    const int nt = (a.F + 31) / 32;  // (q_frames > 64 >= kv_frames is legal too: the key tiles follow kv_frames alone)
+    a.ldv = nt * 32 + 8;
+    const size_t per_head = (size_t)a.dh * a.ldv * sizeof(half_t);
+    a.hg = 1;
+    for (int g = a.heads; g >= 1; --g)
+        if (a.heads % g == 0 && g * per_head <= 64 * 1024) {
+            a.hg = g;
+            break;
+        }
+    a.ngroups = a.heads / a.hg;
+    const size_t lds = a.hg * per_head;
+    if (lds > 160 * 1024 || (int64_t)a.tokens * a.ngroups > 0x7fffffff || batch > 65535) return FZ_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)(a.tokens * a.ngroups), batch), block(TTHREADS);
+    auto launch = [&](auto kern) -> int {
+#ifndef FZ_EMU
+        if (lds > 64 * 1024) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return FZ_ERR_LAUNCH;
+        }
+#endif
+        FZ_LAUNCH(kern, grid, block, lds, stream, a);
+        return fz_last_launch_status();
+    };
+    switch (nt) {
+        case 1: return launch(attn_temporal_long_kernel<1>);
+        case 2: return launch(attn_temporal_long_kernel<2>);
+        case 3: return launch(attn_temporal_long_kernel<3>);
+        case 4: return launch(attn_temporal_long_kernel<4>);
+        case 5: return launch(attn_temporal_long_kernel<5>);
+        case 6: return launch(attn_temporal_long_kernel<6>);
+        case 7: return launch(attn_temporal_long_kernel<7>);
+        case 8: return launch(attn_temporal_long_kernel<8>);
+    }
+    return FZ_ERR_BAD_ARG;
+}
+
 extern "C" int fz_attn_temporal_ex(const void* q, const void* k, const void* v, void* o, int batch, int q_frames,
                                    int kv_frames, int tokens, int heads, int head_dim, int64_t q_row_stride,
                                    int64_t kv_row_stride, int64_t o_row_stride, float scale, void* stream) {
-    if (!q || !k || !v || !o || batch <= 0 || q_frames <= 0 || kv_frames <= 0 || kv_frames > TMAXF || q_frames > TMAXF ||
-        tokens <= 0)
+    if (!q || !k || !v || !o || batch <= 0 || q_frames <= 0 || kv_frames <= 0 || kv_frames > TLONG_MAXF ||
+        q_frames > TLONG_MAXF || tokens <= 0 || heads <= 0 || head_dim <= 0)
         return FZ_ERR_BAD_ARG;
     if ((head_dim & 7) || (q_row_stride & 7) || (kv_row_stride & 7) || (o_row_stride & 7)) return FZ_ERR_BAD_ARG;
+    if (kv_frames > TMAXF || q_frames > TMAXF) {  // long clips: the matrix-pipe kernel.  Up to TMAXF nothing below has changed.
+        TemporalLongArgs l;
+        l.q = (const half_t*)q; l.k = (const half_t*)k; l.v = (const half_t*)v; l.o = (half_t*)o;
+        l.F = kv_frames; l.Fq = q_frames; l.tokens = tokens; l.heads = heads; l.dh = head_dim;
+        l.hg = l.ngroups = l.ldv = 0;
+        l.in_stride = kv_row_stride; l.q_stride = q_row_stride; l.out_stride = o_row_stride; l.scale = scale;
+        return tlong_launch(l, batch, stream);
+    }
     TemporalArgs a;
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.v = (const half_t*)v; a.o = (half_t*)o;
     a.batch = batch; a.F = kv_frames; a.Fq = q_frames; a.tokens = tokens; a.heads = heads; a.dh = head_dim;

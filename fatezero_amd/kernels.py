@@ -14,6 +14,7 @@ from . import _native as N
 FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = N.FZ_ATTN_FLASH, N.FZ_ATTN_CAPTURE, N.FZ_ATTN_INJECT
 CROSS_P_STRIDE = N.FZ_CROSS_P_STRIDE
 CROSS_KEYS = N.FZ_CROSS_MAX_KEYS
+TEMPORAL_MAX_FRAMES = N.FZ_TEMPORAL_MAX_FRAMES
 SUPPORTED_HEAD_DIMS = (16, 32, 40, 64, 80, 128, 160)
 
 
@@ -187,10 +188,13 @@ def attn_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
 def attn_temporal(q, k, v, out, *, batch: int, clip_len: int, heads: int, scale: Optional[float] = None,
                   kv_frames: Optional[int] = None):
     """q,out: [B*clip_len, tokens, >=C]; k,v: [B*kv_frames, tokens, >=C] token-major views (kv_frames defaults to clip_len;
-    it is larger when the clip is frame-sharded and k / v were all-gathered)."""
+    it is larger when the clip is frame-sharded and k / v were all-gathered).  Neither may exceed TEMPORAL_MAX_FRAMES."""
     _, tokens, c = q.shape
     d_head = c // heads
     kv_frames = clip_len if kv_frames is None else kv_frames
+    if max(clip_len, kv_frames) > TEMPORAL_MAX_FRAMES:
+        raise ValueError("temporal attention serves clips of up to %d frames (FZ_TEMPORAL_MAX_FRAMES); got %d query and %d "
+                         "key/value frames" % (TEMPORAL_MAX_FRAMES, clip_len, kv_frames))
     _chk16(q, k, v, out)
     assert k.stride(1) == v.stride(1) and q.stride(0) == tokens * q.stride(1) and k.stride(0) == tokens * k.stride(1)
     assert v.stride(0) == tokens * v.stride(1) and out.stride(0) == tokens * out.stride(1)

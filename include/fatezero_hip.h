@@ -107,14 +107,21 @@ typedef struct FzAttnCrossDesc {
 int fz_attn_cross(const FzAttnCrossDesc* desc, const void* q, const void* k, const void* vt, void* o,
                   void* p, const void* mapper_t, const float* coef, void* cur_out, void* stream);
 
+/* Longest clip temporal attention serves: 8 key tiles of 32 frames, whose scores the long-clip kernel keeps in registers as
+ * whole rows (the exact softmax of the reference: P is normalised before it is rounded to fp16). */
+#define FZ_TEMPORAL_MAX_FRAMES 256
+
 /* Temporal attention over frames (un-patched CrossAttention.forward, attention.py:327-337):
- * q,k,v,o: [B*F][tokens][channels] (row stride given); each (b, token, head) attends over its F frames. */
+ * q,k,v,o: [B*F][tokens][channels] (row stride given); each (b, token, head) attends over its F frames.
+ * Domain: 1 <= clip_len <= FZ_TEMPORAL_MAX_FRAMES, head_dim % 8 == 0, row strides % 8 == 0 (elements); FZ_ERR_BAD_ARG outside it.
+ * Clips of up to 64 frames run the one-thread-per-query-frame kernels, longer ones the matrix-pipe kernel (csrc/attn_temporal.hip). */
 int fz_attn_temporal(const void* q, const void* k, const void* v, void* o, int batch, int clip_len,
                      int tokens, int heads, int head_dim, int64_t qkv_row_stride, int64_t o_row_stride,
                      float scale, void* stream);
 
 /* Same with q/o holding q_frames frames per batch element and k/v holding kv_frames (a frame-sharded clip: the rank's
- * own query frames against the all-gathered keys/values); q/o rows are [B*q_frames][tokens], k/v rows [B*kv_frames][tokens]. */
+ * own query frames against the all-gathered keys/values); q/o rows are [B*q_frames][tokens], k/v rows [B*kv_frames][tokens].
+ * Domain: 1 <= q_frames, kv_frames <= FZ_TEMPORAL_MAX_FRAMES (each on its own; q_frames != kv_frames is the point of this form). */
 int fz_attn_temporal_ex(const void* q, const void* k, const void* v, void* o, int batch, int q_frames, int kv_frames,
                         int tokens, int heads, int head_dim, int64_t q_row_stride, int64_t kv_row_stride,
                         int64_t o_row_stride, float scale, void* stream);

@@ -161,6 +161,31 @@ def temporal_bench():
     print(json.dumps(res))
 
 
+def temporal_long_bench():
+    """Temporal attention on long clips: F = 64 (the one-thread-per-query-frame kernel, unchanged) against F = 96 / 128 (the
+    matrix-pipe kernel) at the four SD-1.x levels.  Per launch: us, ns per (token, head, query frame, key frame) pair, and the
+    fraction of the HBM roof (8 TB/s) on the q + k + v + o bytes.  The shader clock is sampled while the timed loops run."""
+    from bench import SmiSampler
+    dev, res = "cuda", {}
+    smi = SmiSampler(0, period=0.2).start()
+    for (tokens, c) in [(4096, 320), (1024, 640), (256, 1280), (64, 1280)]:
+        for f in (64, 96, 128):
+            qkv = torch.randn(f, tokens, 3 * c).half().to(dev)
+            out = torch.empty(f, tokens, c, dtype=torch.float16, device=dev)
+
+            def run():
+                K.attn_temporal(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], out, batch=1, clip_len=f, heads=8)
+            ms = timeit(run, iters=20, warm=5)
+            ms = timeit(run, iters=max(20, min(2000, int(300.0 / ms))), warm=0)  # ~0.3 s of back-to-back launches
+            pairs, byts = tokens * 8 * f * f, 4 * f * tokens * c * 2
+            res[f"temporal_f{f}_T{tokens}_C{c}"] = {"us": ms * 1e3, "ns_per_pair": ms * 1e6 / pairs, "GBps": byts / ms / 1e6,
+                                                    "hbm_roof_fraction": byts / ms / 1e6 / 8000.0,
+                                                    "TFLOPs": 4.0 * pairs * (c // 8) / ms / 1e9}
+    res["box"] = smi.stop()
+    print(json.dumps(res, indent=1))
+    return res
+
+
 def norms_bench():
     dev, res, F_ = "cuda", {}, 8
     for (n, tokens, c) in [(8, 4096, 320), (16, 4096, 320), (8, 4096, 640), (8, 4096, 960), (8, 1024, 640), (8, 1024, 1920),
@@ -194,6 +219,8 @@ def main():
         return conv64_bench()
     if "--norms" in sys.argv:
         return norms_bench()
+    if "--temporal-long" in sys.argv:
+        return temporal_long_bench()
     if "--temporal" in sys.argv:
         return temporal_bench()
     if "--conv" in sys.argv:
