@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.path.join(HERE, "libfatezero_hip.so")
 
 FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = 0, 1, 2
+FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8 = 3, 4  # fz_attn_self: the map as E5M2 bytes (strides in bytes)
 FZ_MAX_KV_SLOTS = 4
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80

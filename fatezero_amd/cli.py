@@ -103,7 +103,8 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
     test_pipeline_config.setdefault("target", DEFAULT_PIPELINE)
     pipeline = instantiate_from_config(test_pipeline_config, vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
                                        scheduler=DDIMScheduler.from_pretrained(pretrained_model_path, subfolder="scheduler"),
-                                       disk_store=kwargs.get("disk_store", False))
+                                       disk_store=kwargs.get("disk_store", False),
+                                       map_dtype=config_driver.map_dtype_of(editing_config, kwargs.get("map_dtype")))
     pipeline.scheduler.set_timesteps(editing_config["num_inference_steps"])
     pipeline.set_progress_bar_config(disable=True)
     pipeline.print_pipeline(logger)
@@ -168,8 +169,10 @@ def run():
 
     @click.command()
     @click.option("--config", type=str, default="config/sample.yml")
-    def _main(config):
-        run_config_file(config)
+    @click.option("--map-dtype", type=click.Choice(list(config_driver.MAP_DTYPES)), default=None,
+                  help="storage of the captured self-attention maps (default: editing_config.attention_map_dtype, else fp16)")
+    def _main(config, map_dtype):
+        run_config_file(config, **({} if map_dtype is None else {"map_dtype": map_dtype}))
 
     _main()
 

@@ -92,6 +92,18 @@ def load_config(path: str) -> Config:
     return cfg
 
 
+MAP_DTYPES = ("fp16", "e5m2")
+
+
+def map_dtype_of(editing_config: Optional[Dict[str, Any]], override: Optional[str] = None) -> str:
+    """Storage of the captured self-attention maps: `override` (the --map-dtype switch), else the optional
+    `editing_config.attention_map_dtype` key (an extension: no reference config has it), else "fp16"."""
+    value = override if override is not None else (editing_config or {}).get("attention_map_dtype", "fp16")
+    if value not in MAP_DTYPES:
+        raise ValueError("attention_map_dtype must be one of %s, got %r" % (", ".join(repr(m) for m in MAP_DTYPES), value))
+    return value
+
+
 def plan_edits(editing_config: Dict[str, Any], source_prompt: Optional[str]) -> List[Dict[str, Any]]:
     """One dict of pipeline keyword arguments per (editing prompt, seed), in the order the reference runs them."""
     prompts = list(editing_config["editing_prompts"])
@@ -129,6 +141,8 @@ def run_config(pipe, config: Dict[str, Any], *, latents: Optional[torch.Tensor] 
     source_prompt = config.get("dataset_config", {}).get("prompt")
     steps = editing.get("num_inference_steps", 20)
     pipe.scheduler.set_timesteps(steps)
+    if hasattr(pipe, "set_map_dtype"):  # the key is optional: without it the format the pipeline was built with applies (again)
+        pipe.set_map_dtype(map_dtype_of(editing) if "attention_map_dtype" in editing else pipe.default_map_dtype)
     init = None
     inverted = None
     if editing.get("use_invertion_latents", False):  # (sic) the reference's spelling

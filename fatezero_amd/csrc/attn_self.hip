@@ -28,6 +28,32 @@
 #define FZ_MAP_STORE fz_st_h8_nt
 #endif
 #define PSTR 72 /* halves; 144 B = 9 x 16 B (odd) */
+#define PSTR8 80 /* BYTES per row of the 8-bit staging tile: 64 + 16 = 5 x 16 B (odd) */
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// ---- E5M2 storage of the map (FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8) ----------------------------------------------------------
+// An E5M2 number is the top byte of an fp16 number.  Rounding to nearest-even happens on the fp16 BIT PATTERN, two halves per
+// 32-bit word: add 0x7F plus the bit that will become the last kept one, keep the high byte.  P lies in [0, 1] (bit patterns
+// <= 0x3C01), so a carry never leaves its 16-bit half and there is no NaN / Inf case; fp16 subnormals are ordinary bit
+// patterns here.  w0 = halves (e0, e1), w1 = halves (e2, e3) -> the four bytes e0..e3 of the stored row.
+FZ_DEVICE uint32_t fz_e5m2x4(uint32_t w0, uint32_t w1) {
+    const uint32_t r0 = w0 + 0x007F007Fu + ((w0 >> 8) & 0x00010001u);
+    const uint32_t r1 = w1 + 0x007F007Fu + ((w1 >> 8) & 0x00010001u);
+    return ((r0 >> 8) & 0xFFu) | ((r0 >> 16) & 0xFF00u) | ((r1 << 8) & 0xFF0000u) | (r1 & 0xFF000000u);
+}
+// the exact way back: each stored byte becomes the high byte of a half.  w = bytes e0..e3 -> lo = halves (e0, e1), hi = (e2, e3)
+FZ_DEVICE uint32_t fz_e5m2_lo_h2(uint32_t w) { return ((w << 8) & 0xFF00u) | ((w << 16) & 0xFF000000u); }
+FZ_DEVICE uint32_t fz_e5m2_hi_h2(uint32_t w) { return ((w >> 8) & 0xFF00u) | (w & 0xFF000000u); }
+FZ_DEVICE u32x4 fz_ld_b16(const uint8_t* p) { return *reinterpret_cast<const u32x4*>(p); }
+FZ_DEVICE void fz_st_b16(uint8_t* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
+FZ_DEVICE void fz_st_b16_nt(uint8_t* p, u32x4 v) {
+#ifdef FZ_EMU
+    *reinterpret_cast<u32x4*>(p) = v;
+#else
+    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
+#endif
+}
 
 template <int D, int MODE>
 struct SelfCfg {
@@ -46,7 +72,8 @@ struct SelfCfg {
     static constexpr int OS = QBLK * OSTR;
     // CAPTURE: a wave-private 32 x 64 staging tile turns the lanes' 16-byte pieces of 32 different rows into full 128-byte
     // row segments before they leave for HBM (a 16-byte write per lane is a 16-byte L2 request: 17 M requests per 268 MB map)
-    static constexpr int PS = (MODE == FZ_ATTN_CAPTURE) ? 4 * 32 * PSTR : 0;
+    // (CAPTURE8: the same tile in bytes, 32 x 64 B at a row stride of PSTR8 bytes -> full 64-byte row segments)
+    static constexpr int PS = (MODE == FZ_ATTN_CAPTURE) ? 4 * 32 * PSTR : (MODE == FZ_ATTN_CAPTURE8) ? 4 * 32 * PSTR8 / 2 : 0;
     static constexpr int MAIN = 2 * STAGE + PS;
     static constexpr int LDS_HALVES = MAIN > OS ? MAIN : OS;
     static constexpr int KLD = (KVBLK * DCH + 255) / 256;  // 16-byte K chunks per thread per tile
@@ -72,6 +99,9 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                  const half_t* __restrict__ vt, half_t* __restrict__ o, half_t* __restrict__ p,
                  const float* __restrict__ row_mask) {
     typedef SelfCfg<D, MODE> C;
+    constexpr bool CAP = MODE == FZ_ATTN_CAPTURE || MODE == FZ_ATTN_CAPTURE8;
+    constexpr bool INJ = MODE == FZ_ATTN_INJECT || MODE == FZ_ATTN_INJECT8;
+    constexpr bool P8 = MODE == FZ_ATTN_CAPTURE8 || MODE == FZ_ATTN_INJECT8;  // `p` holds E5M2 bytes, its strides count bytes
     FZ_SHARED __attribute__((aligned(16))) half_t smem[C::LDS_HALVES];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq_ = lane & 31, hi = lane >> 5;
@@ -124,7 +154,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
 
     bool use_cur = true;  // INJECT: does this lane's row keep the live attention?
     bool any_cur = true;  // kernel-uniform: is QK^T needed at all?
-    if (MODE == FZ_ATTN_INJECT) {
+    if (INJ) {
         use_cur = false;
         if (row_mask != nullptr && qvalid)
             use_cur = row_mask[(int64_t)(fl + d.mask_frame_off) * d.lq + qrow] != 0.0f;
@@ -134,11 +164,19 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     // ---- the stored map: this lane's 64-byte segment of its row inside the current 64-key tile ----------------------------
     // rows that do not take part (beyond lq; INJECT rows that keep the live attention) are pointed at the tile's first row,
     // so that the loads stay unconditional (a predicated load costs a vmcnt(0) at the join) and hit in L1
-    const bool p_vec = ((d.lkf | d.p_row_stride | d.p_head_stride | d.p_frame_stride) & 7) == 0 &&
+    // (8-bit map: the lane's 32 keys are 32 bytes, two 16-byte pieces -> 16-byte alignment asks for lkf % 16 == 0)
+    const bool p_vec = ((d.lkf | d.p_row_stride | d.p_head_stride | d.p_frame_stride) & (P8 ? 15 : 7)) == 0 &&
                        (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-    const bool p_mine = qvalid && !(MODE == FZ_ATTN_INJECT && use_cur);
-    half_t* prow = p + (int64_t)(fl + d.p_frame_off) * d.p_frame_stride + (int64_t)h * d.p_head_stride +
-                   (int64_t)(p_mine ? qrow : qt * QBLK) * d.p_row_stride + 32 * hi;
+    const bool p_mine = qvalid && !(INJ && use_cur);
+    half_t* prow = nullptr;
+    if (!P8)
+        prow = p + (int64_t)(fl + d.p_frame_off) * d.p_frame_stride + (int64_t)h * d.p_head_stride +
+               (int64_t)(p_mine ? qrow : qt * QBLK) * d.p_row_stride + 32 * hi;
+    uint8_t* const p8 = reinterpret_cast<uint8_t*>(p);
+    uint8_t* prow8 = nullptr;
+    if (P8)
+        prow8 = p8 + (int64_t)(fl + d.p_frame_off) * d.p_frame_stride + (int64_t)h * d.p_head_stride +
+                (int64_t)(p_mine ? qrow : qt * QBLK) * d.p_row_stride + 32 * hi;
 
     // ---- K / V^T tiles: global -> registers (prefetch, one tile ahead) -> LDS (2-stage ring, one barrier per tile) ---------
     half8_t kreg[C::KLD], vreg[C::VLD];
@@ -232,7 +270,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     for (int t = 0; t < C::NT; ++t) oacc[t] = fz_zero_f16v();
 
     // ---- CAPTURE pass 1: exact row max and sum (K tiles only) ------------------------------------------------
-    if (MODE == FZ_ATTN_CAPTURE && !(ABL & 1)) {
+    if (CAP && !(ABL & 1)) {
         fetch(0, true, false);
         stash(0, true, false);
         __syncthreads();
@@ -263,8 +301,9 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     }
 
     // ---- main pass --------------------------------------------------------------------------------------
-    const bool need_k = (MODE != FZ_ATTN_INJECT) || any_cur;
+    const bool need_k = !INJ || any_cur;
     half8_t pst[4];  // INJECT: the stored segment of the NEXT tile, in flight during the current one
+    u32x4 pst8[2];   // INJECT8: the same 32 keys as 32 bytes
     auto fetch_p = [&](int kt) {
         const int j = kt / tps, r0 = (kt % tps) * KVBLK;
         const half_t* sp = prow + (int64_t)j * d.lkf + r0;
@@ -285,8 +324,34 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                 }
         }
     };
+    auto fetch_p8 = [&](int kt) {
+        const int j = kt / tps, r0 = (kt % tps) * KVBLK;
+        const uint8_t* sp = prow8 + (int64_t)j * d.lkf + r0;
+        if (p_vec) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                // a 16-key piece is either entirely inside the row or entirely padding (lkf % 16 == 0): clamp, zero below
+                const int rr = r0 + 32 * hi + 16 * c;
+                pst8[c] = fz_ld_b16(rr < d.lkf ? sp + 16 * c : sp - (r0 + 32 * hi));
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int i = 16 * c + 4 * w + e;
+                        if (r0 + 32 * hi + i < d.lkf) v |= (uint32_t)sp[i] << (8 * e);
+                    }
+                    pst8[c][w] = v;
+                }
+        }
+    };
     fetch(0, need_k, true);
     if (MODE == FZ_ATTN_INJECT) fetch_p(0);
+    if (MODE == FZ_ATTN_INJECT8) fetch_p8(0);
     stash(0, need_k, true);
     __syncthreads();
     for (int kt = 0; kt < ntiles; ++kt) {
@@ -300,16 +365,26 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                 if (p_vec && r0 + KVBLK > d.lkf && r0 + 32 * hi + 8 * c >= d.lkf) pf[c] = fz_zero_h8();
             }
         }
+        if (MODE == FZ_ATTN_INJECT8) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {  // bytes -> halves: each stored byte is the high byte of its half (exact)
+                const uint32_t b0 = pst8[c >> 1][2 * (c & 1)], b1 = pst8[c >> 1][2 * (c & 1) + 1];
+                const u32x4 w = {fz_e5m2_lo_h2(b0), fz_e5m2_hi_h2(b0), fz_e5m2_lo_h2(b1), fz_e5m2_hi_h2(b1)};
+                pf[c] = __builtin_bit_cast(half8_t, w);
+                if (p_vec && r0 + KVBLK > d.lkf && r0 + 32 * hi + 8 * c >= d.lkf) pf[c] = fz_zero_h8();
+            }
+        }
         if (kt + 1 < ntiles) {
             fetch(kt + 1, need_k, true);
             if (MODE == FZ_ATTN_INJECT) fetch_p(kt + 1);
+            if (MODE == FZ_ATTN_INJECT8) fetch_p8(kt + 1);
         }
         float alpha = 1.0f;
         if (need_k) {
             f32x2 s2[16];
             scores(st, r0, s2);
             const f32x2 cs2 = {cs, cs};
-            if (MODE == FZ_ATTN_CAPTURE) {
+            if (CAP) {
                 const f32x2 nm2 = {-m, -m};
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -339,7 +414,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                 half8_t pc;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pc[e] = (half_t)s2[4 * c + e / 2][e & 1];
-                if (MODE == FZ_ATTN_CAPTURE || use_cur) pf[c] = pc;  // per-lane select: lane <-> query row
+                if (CAP || use_cur) pf[c] = pc;  // per-lane select: lane <-> query row
             }
         }
         if (MODE == FZ_ATTN_CAPTURE && !(ABL & 2)) {
@@ -357,7 +432,27 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                         if (r0 + 32 * hi + 8 * c + e < d.lkf) dp[8 * c + e] = pf[c][e];
             }
         }
-        if (MODE == FZ_ATTN_INJECT && any_cur) {
+        if (MODE == FZ_ATTN_CAPTURE8 && !(ABL & 2)) {
+            // only the STORED copy is rounded: pf, the operand of P.V below, keeps the fp16 values of FZ_ATTN_CAPTURE
+            u32x4 qb[2];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const u32x4 w = __builtin_bit_cast(u32x4, pf[c]);
+                qb[c >> 1][2 * (c & 1)] = fz_e5m2x4(w[0], w[1]);
+                qb[c >> 1][2 * (c & 1) + 1] = fz_e5m2x4(w[2], w[3]);
+            }
+            if (p_vec) {
+                uint8_t* Pw = reinterpret_cast<uint8_t*>(smem + 2 * C::STAGE) + wave * 32 * PSTR8;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) fz_st_b16(Pw + lq_ * PSTR8 + 32 * hi + 16 * c, qb[c]);
+            } else if (qvalid) {
+                uint8_t* dp = prow8 + (int64_t)j * d.lkf + r0;
+#pragma unroll
+                for (int i = 0; i < 32; ++i)
+                    if (r0 + 32 * hi + i < d.lkf) dp[i] = (uint8_t)(qb[i >> 4][(i >> 2) & 3] >> (8 * (i & 3)));
+            }
+        }
+        if (INJ && any_cur) {
 #pragma unroll
             for (int t = 0; t < C::NT; ++t) oacc[t] *= alpha;
         }
@@ -396,12 +491,27 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
             }
             fz_wave_lds_sync();  // the staging tile is free again for the next step's writes (same wave)
         }
+        if (MODE == FZ_ATTN_CAPTURE8 && !(ABL & 2) && p_vec) {
+            // as above (after the stash); full 64-byte row segments: 4 lanes per row, 16 rows per pass
+            const uint8_t* Pw = reinterpret_cast<const uint8_t*>(smem + 2 * C::STAGE) + wave * 32 * PSTR8;
+            fz_wave_lds_sync();
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int row = 16 * i + (lane >> 2), ch = lane & 3;
+                const int qg = qt * QBLK + wave * 32 + row;
+                if (qg < d.lq && r0 + 16 * ch < d.lkf)
+                    fz_st_b16_nt(p8 + (int64_t)(fl + d.p_frame_off) * d.p_frame_stride + (int64_t)h * d.p_head_stride +
+                                     (int64_t)qg * d.p_row_stride + (int64_t)j * d.lkf + r0 + 16 * ch,
+                                 fz_ld_b16(Pw + row * PSTR8 + 16 * ch));
+            }
+            fz_wave_lds_sync();
+        }
         __syncthreads();
     }
 
     // ---- epilogue: normalise, stage O^T through LDS, store whole head-rows -----------------------------
     float fin = 1.0f;
-    if (MODE == FZ_ATTN_INJECT && any_cur) {
+    if (INJ && any_cur) {
         l += fz_shfl_xor(l, 32);
         if (use_cur) fin = 1.0f / l;
     }
@@ -444,6 +554,12 @@ static int launch_self(const FzAttnSelfDesc& d, const void* q, const void* k, co
         case FZ_ATTN_INJECT:
             FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_INJECT>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
             break;
+        case FZ_ATTN_CAPTURE8:
+            FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_CAPTURE8>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
+            break;
+        case FZ_ATTN_INJECT8:
+            FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_INJECT8>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
+            break;
         default:
             return FZ_ERR_BAD_ARG;
     }
@@ -459,7 +575,7 @@ extern "C" int fz_attn_self(const FzAttnSelfDesc* desc, const void* q, const voi
     const FzAttnSelfDesc& d = *desc;
     if (d.n_frames <= 0 || d.lq <= 0 || d.lkf <= 0 || d.n_kv < 1 || d.n_kv > FZ_MAX_KV_SLOTS) return FZ_ERR_BAD_ARG;
     if (d.mode != FZ_ATTN_FLASH && !p) return FZ_ERR_BAD_ARG;
-    if (!(d.mode == FZ_ATTN_INJECT && row_mask == nullptr) && !k) return FZ_ERR_BAD_ARG;
+    if (!((d.mode == FZ_ATTN_INJECT || d.mode == FZ_ATTN_INJECT8) && row_mask == nullptr) && !k) return FZ_ERR_BAD_ARG;
     if ((d.q_row_stride | d.k_row_stride | d.vt_chan_stride | d.o_row_stride | d.q_frame_stride | d.k_frame_stride |
          d.vt_frame_stride | d.o_frame_stride) & 7)
         return FZ_ERR_BAD_ARG;  // 16-byte vector access

@@ -310,7 +310,7 @@ class IssuePlans:
             if sig is None:
                 return None
         return (tuple(x.data.shape), x.b, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
-                ctx.dtype, type(controller), sig, _model_switches())
+                ctx.dtype, type(controller), sig, _model_switches())  # (sig carries the map format)
 
     # -- record --------------------------------------------------------------------------------------------
     @classmethod

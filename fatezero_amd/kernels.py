@@ -12,6 +12,8 @@ import torch
 from . import _native as N
 
 FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = N.FZ_ATTN_FLASH, N.FZ_ATTN_CAPTURE, N.FZ_ATTN_INJECT
+FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8 = N.FZ_ATTN_CAPTURE8, N.FZ_ATTN_INJECT8
+MAP8_DTYPES = (torch.uint8, torch.float8_e5m2)  # storage of an E5M2 self-attention map (one byte per probability)
 CROSS_P_STRIDE = N.FZ_CROSS_P_STRIDE
 CROSS_KEYS = N.FZ_CROSS_MAX_KEYS
 TEMPORAL_MAX_FRAMES = N.FZ_TEMPORAL_MAX_FRAMES
@@ -65,6 +67,23 @@ def pad64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+def e5m2_to_half(b: torch.Tensor) -> torch.Tensor:
+    """The fp16 tensor an E5M2 map stands for (exact: each byte is the high byte of a half)."""
+    return b.view(torch.uint8).to(torch.int16).bitwise_left_shift(8).view(torch.float16)
+
+
+def half_to_e5m2(x: torch.Tensor) -> torch.Tensor:
+    """fp16 -> E5M2 bytes, round-to-nearest-even: what FZ_ATTN_CAPTURE8 stores for the fp16 map FZ_ATTN_CAPTURE stores."""
+    return x.to(torch.float16).to(torch.float8_e5m2).view(torch.uint8)
+
+
+def self_mode_for(mode: int, p: Optional[torch.Tensor]) -> int:
+    """FZ_ATTN_CAPTURE / FZ_ATTN_INJECT, or their 8-bit forms when `p` is an E5M2 map."""
+    if p is not None and p.dtype in MAP8_DTYPES:
+        return {FZ_ATTN_CAPTURE: FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT: FZ_ATTN_INJECT8}.get(mode, mode)
+    return mode
+
+
 # ------------------------------------------------------------------------------------------------------------
 # sparse-causal self attention
 # ------------------------------------------------------------------------------------------------------------
@@ -99,7 +118,8 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
               mask_frame_off: int = 0, scale: Optional[float] = None, k_head_major: Optional[torch.Tensor] = None,
               q_log2_scaled: bool = False, kv_slots_override: Optional[Tuple[List[int], List[int]]] = None,
               kv_clip_len: int = 0, kv_frame_off: int = 0):
-    """q,k,out: [N, L, >=C] views with row stride (token-major); vt: [N, C, Lpad]; p: [Fp, heads, Lq, Lk] fp16.
+    """q,k,out: [N, L, >=C] views with row stride (token-major); vt: [N, C, Lpad]; p: [Fp, heads, Lq, Lk] fp16 -- or, for
+    mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8, the same shape in one-byte storage (torch.uint8 or torch.float8_e5m2: E5M2).
     k_head_major (optional): K as a contiguous [N, heads, L, d] tensor (fully coalesced key tiles) instead of `k`.
 
     q_log2_scaled: q already carries scale*log2(e) (folded into the projection weight), see include/fatezero_hip.h.
@@ -111,7 +131,16 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
     N_, lq, c = q.shape
     d_head = c // heads
     assert d_head in SUPPORTED_HEAD_DIMS, d_head
-    _chk16(q, k, vt, out, p)
+    map8 = mode in (FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8)
+    if map8:
+        if p is None or p.dtype not in MAP8_DTYPES:
+            raise TypeError("FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8 take the map as torch.uint8 or torch.float8_e5m2 storage, got %s"
+                            % (None if p is None else p.dtype))
+        _chk16(q, k, vt, out)
+    else:
+        if p is not None and p.dtype in MAP8_DTYPES:
+            raise TypeError("an 8-bit map needs mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8 (kernels.self_mode_for)")
+        _chk16(q, k, vt, out, p)
     n_frames = N_ - frame0 if n_frames is None else n_frames
     kabs, kval = kv_slots(index_list, clip_len) if kv_slots_override is None else kv_slots_override
     d = N.FzAttnSelfDesc()
@@ -138,7 +167,11 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
     d.o_frame_stride, d.o_row_stride = out.stride(0), out.stride(1)
     if p is not None:
         assert p.stride(3) == 1 and p.shape[3] == d.n_kv * d.lkf, (p.shape, d.n_kv, d.lkf)
+        # (one-byte elements: the element strides of an 8-bit map ARE the byte strides the 8-bit modes ask for)
         d.p_frame_stride, d.p_head_stride, d.p_row_stride = p.stride(0), p.stride(1), p.stride(2)
+        if map8:
+            assert p.element_size() == 1 and p.shape[0] >= p_frame_off + n_frames and p.shape[1] == heads and p.shape[2] == lq, p.shape
+            assert min(p.stride(0), p.stride(1), p.stride(2)) >= 0 and p.stride(2) >= p.shape[3], p.stride()
     d.p_frame_off, d.mask_frame_off = p_frame_off, mask_frame_off
     if row_mask is not None:
         assert row_mask.dtype == torch.float32 and row_mask.is_contiguous() and row_mask.shape[-1] == lq

@@ -445,9 +445,10 @@ class SparseCausalAttention(CrossAttention):
             if plan.n_plain < n:
                 rest = dict(frame0=plan.n_plain, n_frames=n - plan.n_plain)
                 if plan.capture_first is not None:  # edit pass with save_self_attention: keep the live map too
-                    K.attn_self(q, kk, vt, out, mode=K.FZ_ATTN_CAPTURE, p=plan.capture_first, **rest, **kw)
-                if plan.mode == K.FZ_ATTN_INJECT:
-                    K.attn_self(q, kk if plan.row_mask is not None else None, vt, out, mode=K.FZ_ATTN_INJECT, p=plan.p,
+                    K.attn_self(q, kk, vt, out, mode=K.self_mode_for(K.FZ_ATTN_CAPTURE, plan.capture_first), p=plan.capture_first,
+                                **rest, **kw)
+                if plan.mode in (K.FZ_ATTN_INJECT, K.FZ_ATTN_INJECT8):  # (INJECT8: the stored map is E5M2 bytes)
+                    K.attn_self(q, kk if plan.row_mask is not None else None, vt, out, mode=plan.mode, p=plan.p,
                                 row_mask=plan.row_mask, **rest, **kw)
                 elif not (plan.mode == K.FZ_ATTN_FLASH and plan.capture_first is not None):
                     K.attn_self(q, kk, vt, out, mode=plan.mode, p=plan.p, **rest, **kw)

@@ -59,9 +59,12 @@ class _LatentState:
 
 
 class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
-    def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, disk_store: bool = False):
+    def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, disk_store: bool = False, map_dtype: str = "fp16"):
+        """`map_dtype` (extension): "fp16" (default) or "e5m2" -- the captured SELF-attention maps at one byte per probability, which
+        halves the map arena (attention_store.py); cross maps, the inversion trajectory and every other tensor are unaffected."""
         super().__init__(vae, text_encoder, tokenizer, unet, scheduler)
-        self.store_controller = attention_util.AttentionStore(disk_store=disk_store)
+        self.map_dtype = self.default_map_dtype = map_dtype  # (default_map_dtype: what a YAML config without the key falls back to)
+        self.store_controller = attention_util.AttentionStore(disk_store=disk_store, map_dtype=map_dtype)
         self.empty_controller = attention_util.EmptyControl()
         # extension: a fatezero_amd.dist.FrameShard splits the clip's frames over the ranks of a process group; every rank
         # is handed (and returns) the full latents, keeps only its own frames' maps / masks in between
@@ -75,6 +78,14 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         full = shard.all_gather_frames(x.permute(0, 1, 3, 2, 4, 5).reshape(s_ * b_, fl, c_, h_, w_))
         full = full.reshape(s_, b_, shard.clip_len, c_, h_, w_).permute(0, 1, 3, 2, 4, 5)
         return [full[i].contiguous() for i in range(s_)]
+
+    def set_map_dtype(self, map_dtype: str):
+        """Switch the storage of the captured self-attention maps ("fp16" | "e5m2") for the jobs that follow: the maps of the last
+        inversion are dropped and a store of the new format takes the old one's place."""
+        if map_dtype != self.map_dtype:
+            store = self.store_controller.with_map_dtype(map_dtype)  # (raises on an unknown name)
+            self.release_attention_maps()
+            self.store_controller, self.map_dtype = store, map_dtype
 
     def release_attention_maps(self):
         """Free the HBM map arena of the last inversion (and the edit controller that references it) so that the next
@@ -185,7 +196,8 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
             additional_attention_store=self.store_controller, use_inversion_attention=kwargs["use_inversion_attention"],
             blend_th=kwargs.get("blend_th", (0.3, 0.3)), blend_self_attention=kwargs.get("blend_self_attention", None),
             blend_latents=kwargs.get("blend_latents", None), save_path=kwargs.get("save_path", None),
-            save_self_attention=kwargs.get("save_self_attention", True), disk_store=kwargs.get("disk_store", False))
+            save_self_attention=kwargs.get("save_self_attention", True), disk_store=kwargs.get("disk_store", False),
+            map_dtype=kwargs.get("map_dtype") or self.map_dtype)
         attention_util.register_attention_control(self, edit_controller)
         self.last_edit_controller = edit_controller
         sdimage_output = self.sd_ddim_pipeline(controller=edit_controller, **kwargs)

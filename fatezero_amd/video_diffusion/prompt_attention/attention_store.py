@@ -15,6 +15,11 @@ Differences, by design: the running sum `attention_store` (attention_store.py:95
 cross maps unless `accumulate_self=True` (its self-attention entries have no live consumer in the reference);
 `latents_store` stays on the device; `disk_store=True` spills the steps that do not fit the HBM budget to pinned host memory (MapArena)
 instead of writing .pt files.
+
+`map_dtype="e5m2"` (opt-in; the default "fp16" is the layout above) stores the SELF-attention maps at one byte per probability: the
+attention kernel rounds each fp16 value to E5M2 -- the top byte of the half -- as it writes (FZ_ATTN_CAPTURE8) and the edit reads the bytes
+back (FZ_ATTN_INJECT8).  Cross maps stay fp16.  Every reference-shaped reader (`attention_store_all_step`, `CapturedMap.view`, the running
+sum with `accumulate_self`) sees fp16 tensors dequantised exactly from the bytes, built when they are read.
 """
 import abc
 import os
@@ -26,6 +31,7 @@ from ... import kernels as K
 from ..models.attention import AttnPlan
 
 KEYS = ("down_cross", "mid_cross", "up_cross", "down_self", "mid_self", "up_self")
+MAP_DTYPES = ("fp16", "e5m2")  # storage of the captured self-attention maps
 MAX_CONTROLLED_TOKENS = 32 ** 2  # attention_store.py:83, attention_util.py:104
 
 
@@ -107,34 +113,6 @@ class SpilledStep:
         ev, self.d2h_event = self.d2h_event, None
         if ev is not None:
             ev.synchronize()
-
-
-class HostStepMaps(dict):
-    """`attention_store_all_step[step]` of a spilled step: {key: [host views]} whose first read waits for the device-to-host copy that is
-    still in flight when the capture pass hands the views out (the reference's `.cpu()` blocks at once, attention_store.py:86-87)."""
-
-    def __init__(self, items, spilled_step):
-        super().__init__(items)
-        self._sp = spilled_step
-
-    def _ready(self):
-        self._sp.wait_host()
-
-    def __getitem__(self, k):
-        self._ready()
-        return super().__getitem__(k)
-
-    def get(self, k, default=None):
-        self._ready()
-        return super().get(k, default)
-
-    def items(self):
-        self._ready()
-        return super().items()
-
-    def values(self):
-        self._ready()
-        return super().values()
 
 
 class MapArena:
@@ -264,15 +242,17 @@ class MapArena:
         self.total_bytes += want
         return slab
 
-    def alloc(self, shape, device):
-        nbytes = 2
+    def alloc(self, shape, device, itemsize=2):
+        """A map of `shape` in the step being captured: fp16 (itemsize 2) or one byte per element (itemsize 1: a uint8 tensor)."""
+        dtype = torch.float16 if itemsize == 2 else torch.uint8
+        nbytes = itemsize
         for s in shape:
             nbytes *= s
         nbytes = (nbytes + 255) // 256 * 256
         if not self.first_step_done:
             self.step_bytes += nbytes
             self.total_bytes += nbytes
-            return torch.empty(shape, dtype=torch.float16, device=device)
+            return torch.empty(shape, dtype=dtype, device=device)
         if self.cur is None or self.cur_off + nbytes > self.cur.numel():
             if self.cur is not None and self._cur_slot is not None:
                 raise RuntimeError("spill tier: a step overflows its staging slab (the capture layout grew after the first step): the host copy "
@@ -285,7 +265,7 @@ class MapArena:
                 self._cur_slot = self._claim_slot(device, for_step=self.step)
                 self.cur = self.ring[self._cur_slot]
             self.cur_off = 0
-        out = self.cur[self.cur_off: self.cur_off + 2 * _numel(shape)].view(torch.float16).view(shape)
+        out = self.cur[self.cur_off: self.cur_off + itemsize * _numel(shape)].view(dtype).view(shape)
         self.cur_off += nbytes
         return out
 
@@ -399,17 +379,84 @@ def _numel(shape):
 
 class CapturedMap:
     """One captured map: `storage` is what the kernels address ([F, heads, Lq, 80] for cross maps), `view` is the
-    reference-shaped tensor handed to users ([F, heads, Lq, 77])."""
-    __slots__ = ("storage", "view")
+    reference-shaped tensor handed to users ([F, heads, Lq, 77]).  An 8-bit self map (`map_dtype="e5m2"`) has uint8 `storage`;
+    its `view` is the fp16 tensor the bytes stand for, dequantised (exactly) at every read -- no fp16 copy is kept."""
+    __slots__ = ("storage", "lk", "_view")
 
     def __init__(self, storage, lk):
-        self.storage = storage
-        self.view = storage[..., :lk] if storage.shape[-1] != lk else storage
+        self.storage, self.lk = storage, lk
+        self._view = None if self.is_8bit else (storage[..., :lk] if storage.shape[-1] != lk else storage)
+
+    @property
+    def is_8bit(self):
+        return self.storage.dtype in K.MAP8_DTYPES
+
+    def half(self):
+        """`storage` as fp16 (itself, or the dequantised bytes)."""
+        return K.e5m2_to_half(self.storage) if self.is_8bit else self.storage
+
+    @property
+    def view(self):
+        if self._view is not None:
+            return self._view
+        h = self.half()
+        return h[..., :self.lk] if h.shape[-1] != self.lk else h
+
+
+class LazyStepMaps(dict):
+    """One step's maps as the reference's API promises them -- {key: [fp16 tensors]} -- over CapturedMap entries whose fp16 form exists only
+    while it is read (8-bit storage).  Every read of a key (`d[key]`, `get`, `items`, `values`) returns a NEW plain list of real fp16
+    tensors, dequantised at that moment: it can go to torch.cat / torch.stack, be concatenated, copied or kept; dropping it frees the fp16
+    copies.  The entries themselves (`raw(key)`) are what the store appends to."""
+
+    @staticmethod
+    def _tensors(items):
+        return [x.view if isinstance(x, CapturedMap) else x for x in items]
+
+    def raw(self, k):
+        return dict.__getitem__(self, k)
+
+    def __getitem__(self, k):
+        return self._tensors(dict.__getitem__(self, k))
+
+    def get(self, k, default=None):
+        return self[k] if k in self else default
+
+    def items(self):
+        return [(k, self[k]) for k in self.keys()]
+
+    def values(self):
+        return [self[k] for k in self.keys()]
+
+    def copy(self):
+        return {k: self[k] for k in self.keys()}
+
+
+class HostStepMaps(LazyStepMaps):
+    """`attention_store_all_step[step]` of a spilled step: {key: [host views]} whose first read waits for the device-to-host copy that is
+    still in flight when the capture pass hands the views out (the reference's `.cpu()` blocks at once, attention_store.py:86-87)."""
+
+    def __init__(self, items, spilled_step):
+        super().__init__(items)
+        self._sp = spilled_step
+
+    def __getitem__(self, k):
+        self._sp.wait_host()
+        return super().__getitem__(k)
+
+
+def _views(cms):
+    """fp16 maps: the views themselves; 8-bit maps: the entries, dequantised when the step dict is read (LazyStepMaps)."""
+    return list(cms) if any(cm.is_8bit for cm in cms) else [cm.view for cm in cms]
 
 
 class AttentionStore(AttentionControl):
-    def __init__(self, save_self_attention: bool = True, disk_store=False, accumulate_self: bool = False, hbm_budget_bytes=None):
+    def __init__(self, save_self_attention: bool = True, disk_store=False, accumulate_self: bool = False, hbm_budget_bytes=None,
+                 map_dtype: str = "fp16"):
         super().__init__()
+        if map_dtype not in MAP_DTYPES:
+            raise ValueError("map_dtype must be one of %s, got %r" % (", ".join(repr(m) for m in MAP_DTYPES), map_dtype))
+        self.map_dtype = map_dtype  # "e5m2": self-attention maps at one byte per probability (cross maps stay fp16)
         # The reference's disk_store=True writes every step's maps to ./trash/attention_cache_*/NNN.pt and loads them back in the edit
         # (attention_store.py:103-108, attention_util.py:115-116).  Here it switches the arena's spill tier on: steps stay in HBM while they
         # fit (`hbm_budget_bytes`, or FZ_ARENA_HBM_GB, or 90 % of what the device has free), the rest goes to pinned host memory behind the
@@ -448,9 +495,15 @@ class AttentionStore(AttentionControl):
     def new_slot(self, key, frames, heads, lq, lk, is_cross, device) -> CapturedMap:
         width = K.CROSS_P_STRIDE if is_cross else lk
         self._device = device
-        cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device), lk)
+        map8 = self.map_dtype == "e5m2" and not is_cross
+        cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device, itemsize=1 if map8 else 2), lk)
         self._step_maps[key].append(cm)
-        self.step_store[key].append(cm.view)
+        if self.map_dtype == "e5m2":
+            if not isinstance(self.step_store, LazyStepMaps):
+                self.step_store = LazyStepMaps(self.step_store)
+            self.step_store.raw(key).append(cm if map8 else cm.view)  # 8-bit entries are read back as fp16, dequantised at the read
+        else:
+            self.step_store[key].append(cm.view)
         return cm
 
     def plan_controlled(self, is_cross, place, n_ctrl, clip_len, heads, lq, lk, device) -> AttnPlan:
@@ -458,7 +511,7 @@ class AttentionStore(AttentionControl):
             return AttnPlan(0)
         key = f"{place}_{'cross' if is_cross else 'self'}"
         cm = self.new_slot(key, n_ctrl, heads, lq, lk, is_cross, device)
-        return AttnPlan(0, K.FZ_ATTN_CAPTURE, p=cm.storage)
+        return AttnPlan(0, K.self_mode_for(K.FZ_ATTN_CAPTURE, cm.storage), p=cm.storage)
 
     @property
     def issue_events_first(self):
@@ -468,7 +521,7 @@ class AttentionStore(AttentionControl):
     def issue_signature(self):
         if type(self).plan_controlled is not AttentionStore.plan_controlled:
             return None  # a subclass that plans differently says so itself
-        return ("store", bool(self.LOW_RESOURCE), bool(self.save_self_attention))
+        return ("store", bool(self.LOW_RESOURCE), bool(self.save_self_attention), self.map_dtype)
 
     def forward(self, attn, is_cross: bool, place_in_unet: str):
         """Reference tensor protocol (attention_store.py:81-93): keep a copy of the map."""
@@ -478,7 +531,10 @@ class AttentionStore(AttentionControl):
             cm = self.new_slot(key, f, heads, lq, lk, is_cross, attn.device)
             if cm.storage.shape[-1] != lk:
                 cm.storage[..., lk:] = 0
-            cm.view.copy_(attn)
+            if cm.is_8bit:
+                cm.storage.copy_(K.half_to_e5m2(attn))
+            else:
+                cm.view.copy_(attn)
         return attn
 
     def between_steps(self):
@@ -489,13 +545,13 @@ class AttentionStore(AttentionControl):
             self._sum_storage = {k: [] for k in KEYS}
             for k in keys:
                 for cm in self._step_maps[k]:
-                    s = cm.storage.float()
+                    s = cm.half().float()
                     self._sum_storage[k].append(s)
                     self.attention_store[k].append(s[..., : cm.view.shape[-1]] if s.shape[-1] != cm.view.shape[-1] else s)
         else:
             for k in keys:
                 for acc, cm in zip(self._sum_storage[k], self._step_maps[k]):
-                    K.accumulate(acc, cm.storage)
+                    K.accumulate(acc, cm.half())
         self.attention_store_all_step.append(self.step_store)
         self._all_step_maps.append(self._step_maps)
         self.step_store = self.get_empty_store()
@@ -526,17 +582,25 @@ class AttentionStore(AttentionControl):
         maps, layout, base = self._all_step_maps[step], [], slab.data_ptr()
         for k in KEYS:
             for cm in maps[k]:
-                layout.append((k, cm.storage.data_ptr() - base, tuple(cm.storage.shape), cm.view.shape[-1]))
+                layout.append((k, cm.storage.data_ptr() - base, tuple(cm.storage.shape), cm.lk, cm.storage.element_size()))
         sp = self.arena.spill_step(layout, slab.device)
-        self.attention_store_all_step[step] = HostStepMaps({k: [cm.view for cm in v] for k, v in self._maps_over(sp.host, layout).items()}, sp)
+        self.attention_store_all_step[step] = HostStepMaps({k: _views(v) for k, v in self._maps_over(sp.host, layout).items()}, sp)
         self._all_step_maps[step] = None  # resolved through the arena from here on (maps_of_step)
 
     @staticmethod
     def _maps_over(slab, layout):
         out = {k: [] for k in KEYS}
-        for k, off, shape, lk in layout:
-            out[k].append(CapturedMap(slab[off: off + 2 * _numel(shape)].view(torch.float16).view(shape), lk))
+        for k, off, shape, lk, itemsize in layout:  # (the 8-bit slabs travel through the spill tier as they are)
+            raw = slab[off: off + itemsize * _numel(shape)]
+            out[k].append(CapturedMap((raw.view(torch.float16) if itemsize == 2 else raw).view(shape), lk))
         return out
+
+    def with_map_dtype(self, map_dtype: str):
+        """A fresh store of this one's settings with another map format (this one's maps are not carried over)."""
+        st = AttentionStore(save_self_attention=self.save_self_attention, disk_store=self.disk_store, accumulate_self=self.accumulate_self,
+                            hbm_budget_bytes=self.hbm_budget_bytes, map_dtype=map_dtype)
+        st.LOW_RESOURCE = self.LOW_RESOURCE
+        return st
 
     def maps_of_step(self, step_in_store) -> Dict[str, List[CapturedMap]]:
         if step_in_store < 0:

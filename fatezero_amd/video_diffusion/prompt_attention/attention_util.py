@@ -53,8 +53,8 @@ from .visualization import show_cross_attention  # noqa: E402,F401  (attention_u
 class AttentionControlEdit(AttentionStore, abc.ABC):
     def __init__(self, prompts, num_steps: int, cross_replace_steps, self_replace_steps, latent_blend: Optional[SpatialBlender],
                  tokenizer=None, additional_attention_store: AttentionStore = None, use_inversion_attention: bool = False,
-                 attention_blend: SpatialBlender = None, save_self_attention: bool = True, disk_store=False):
-        super().__init__(save_self_attention=save_self_attention, disk_store=disk_store)
+                 attention_blend: SpatialBlender = None, save_self_attention: bool = True, disk_store=False, map_dtype: str = "fp16"):
+        super().__init__(save_self_attention=save_self_attention, disk_store=disk_store, map_dtype=map_dtype)
         self.additional_attention_store = additional_attention_store
         self.batch_size = len(prompts)
         self.attention_blend = attention_blend
@@ -125,7 +125,8 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
             return None
         in_self_window = self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]
         return ("edit", bool(self.LOW_RESOURCE), bool(self.save_self_attention), bool(in_self_window), self.attention_blend is not None,
-                bool(self.track_cross_attention), self.visualize_res)
+                bool(self.track_cross_attention), self.visualize_res, self.map_dtype,
+                getattr(self.additional_attention_store, "map_dtype", "fp16"))
 
     def plan_controlled(self, is_cross, place, n_ctrl, clip_len, heads, lq, lk, device) -> AttnPlan:
         if lq > MAX_CONTROLLED_TOKENS:
@@ -147,7 +148,7 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         if self.save_self_attention:  # only outside the 'swap' flow of the reference's validation loop
             plan.capture_first = self.new_slot(key, n_ctrl, heads, lq, lk, False, device).storage
         if self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]:
-            plan.mode, plan.p = K.FZ_ATTN_INJECT, base.storage
+            plan.mode, plan.p = K.self_mode_for(K.FZ_ATTN_INJECT, base.storage), base.storage  # (INJECT8 over an E5M2 map)
             if self.attention_blend is not None:
                 h = int(np.sqrt(lq))
                 mask = self.attention_blend(target_h=h, target_w=h, attention_store=step_maps, step_in_store=sis)
@@ -227,10 +228,11 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
 class AttentionReplace(AttentionControlEdit):
     def __init__(self, prompts, num_steps: int, cross_replace_steps, self_replace_steps, latent_blend=None, tokenizer=None,
                  additional_attention_store=None, use_inversion_attention=False, attention_blend=None,
-                 save_self_attention: bool = True, disk_store=False):
+                 save_self_attention: bool = True, disk_store=False, map_dtype: str = "fp16"):
         super().__init__(prompts, num_steps, cross_replace_steps, self_replace_steps, latent_blend, tokenizer=tokenizer,
                          additional_attention_store=additional_attention_store, use_inversion_attention=use_inversion_attention,
-                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store)
+                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store,
+                         map_dtype=map_dtype)
         self.mapper = seq_aligner.get_replacement_mapper(prompts, tokenizer)  # [1, 77, 77]
 
     def mapper_matrix(self):
@@ -243,10 +245,11 @@ class AttentionReplace(AttentionControlEdit):
 class AttentionRefine(AttentionControlEdit):
     def __init__(self, prompts, num_steps: int, cross_replace_steps, self_replace_steps, latent_blend=None, tokenizer=None,
                  additional_attention_store=None, use_inversion_attention=False, attention_blend=None,
-                 save_self_attention: bool = True, disk_store=False):
+                 save_self_attention: bool = True, disk_store=False, map_dtype: str = "fp16"):
         super().__init__(prompts, num_steps, cross_replace_steps, self_replace_steps, latent_blend, tokenizer=tokenizer,
                          additional_attention_store=additional_attention_store, use_inversion_attention=use_inversion_attention,
-                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store)
+                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store,
+                         map_dtype=map_dtype)
         self.mapper, alphas = seq_aligner.get_refinement_mapper(prompts, tokenizer)
         self.alphas = alphas.reshape(alphas.shape[0], 1, 1, alphas.shape[1])
 
@@ -268,10 +271,12 @@ class AttentionReweight(AttentionControlEdit):
 
     def __init__(self, prompts, num_steps: int, cross_replace_steps, self_replace_steps, equalizer, latent_blend=None,
                  controller: Optional[AttentionControlEdit] = None, tokenizer=None, additional_attention_store=None,
-                 use_inversion_attention=False, attention_blend=None, save_self_attention: bool = True, disk_store=False):
+                 use_inversion_attention=False, attention_blend=None, save_self_attention: bool = True, disk_store=False,
+                 map_dtype: str = "fp16"):
         super().__init__(prompts, num_steps, cross_replace_steps, self_replace_steps, latent_blend, tokenizer=tokenizer,
                          additional_attention_store=additional_attention_store, use_inversion_attention=use_inversion_attention,
-                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store)
+                         attention_blend=attention_blend, save_self_attention=save_self_attention, disk_store=disk_store,
+                         map_dtype=map_dtype)
         self.equalizer = equalizer
         self.prev_controller = controller
 
@@ -301,8 +306,9 @@ def make_controller(tokenizer, prompts: List[str], is_replace_controller: bool, 
                     self_replace_steps: float = 0.0, blend_words=None, equilizer_params=None,
                     additional_attention_store=None, use_inversion_attention=False, blend_th=(0.3, 0.3),
                     NUM_DDIM_STEPS=None, blend_latents=False, blend_self_attention=False, save_path=None,
-                    save_self_attention=True, disk_store=False) -> AttentionControlEdit:
-    """attention_util.py:320-387.  `save_path` feeds the blend-mask PNG dumps (`<save_path>/latent_blend_mask`,
+                    save_self_attention=True, disk_store=False, map_dtype="fp16") -> AttentionControlEdit:
+    """attention_util.py:320-387.  `map_dtype` ("fp16" | "e5m2"): storage of the self-attention maps the edit pass itself keeps
+    (save_self_attention); what it READS is in the format of `additional_attention_store`, whatever this says.  `save_path` feeds the blend-mask PNG dumps (`<save_path>/latent_blend_mask`,
     `<save_path>/attention_blend_mask`, written off the hot loop: spatial_blend.py); unlike the reference, `save_path=None`
     together with `blend_words` is accepted and simply dumps nothing."""
     latent_blend = attention_blend = None
@@ -318,7 +324,7 @@ def make_controller(tokenizer, prompts: List[str], is_replace_controller: bool, 
     common = dict(cross_replace_steps=cross_replace_steps, self_replace_steps=self_replace_steps, latent_blend=latent_blend,
                   tokenizer=tokenizer, additional_attention_store=additional_attention_store,
                   use_inversion_attention=use_inversion_attention, attention_blend=attention_blend,
-                  save_self_attention=save_self_attention, disk_store=disk_store)
+                  save_self_attention=save_self_attention, disk_store=disk_store, map_dtype=map_dtype)
     cls = AttentionReplace if is_replace_controller else AttentionRefine
     controller = cls(prompts, NUM_DDIM_STEPS, **common)
     if equilizer_params is not None:

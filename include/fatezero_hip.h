@@ -25,6 +25,12 @@ extern "C" {
 #define FZ_ATTN_FLASH 0   /* O = softmax(scale QK^T) V, no map materialised                       */
 #define FZ_ATTN_CAPTURE 1 /* same, and the fp16 probability map is written to `p` (exact softmax) */
 #define FZ_ATTN_INJECT 2  /* rows take P from `p` (inversion-time map) instead of the live softmax */
+/* fz_attn_self only: the same two with the map stored as E5M2 bytes (the top byte of each fp16 probability, rounded to
+ * nearest-even on the fp16 bit pattern; reading back is exact).  `p` points at bytes and p_frame_stride, p_head_stride and
+ * p_row_stride count bytes.  The launch's output `o` of CAPTURE8 is bit-identical to FZ_ATTN_CAPTURE: only the stored copy is
+ * rounded.  16-byte row pieces need lkf and the three strides to be multiples of 16 (otherwise an element-wise path runs). */
+#define FZ_ATTN_CAPTURE8 3
+#define FZ_ATTN_INJECT8 4
 
 #define FZ_MAX_KV_SLOTS 4
 
