@@ -61,11 +61,6 @@ class FzGemmDesc(C.Structure):
     ]
 
 
-class FzGemmLn(C.Structure):
-    _fields_ = [("stats_in", C.c_void_p), ("c1", C.c_void_p), ("c0", C.c_void_p), ("eps", C.c_float), ("reserved0", C.c_int32),
-                ("stats_out", C.c_void_p)]
-
-
 class FzXattnChain(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("res", C.c_void_p), ("packed", C.c_void_p), ("kv_packed", C.c_void_p), ("bias_out", C.c_void_p),
@@ -96,7 +91,6 @@ _SIGS = {
     "fz_xattn_chain_kv_pack": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "fz_xattn_chain": (C.c_int, [C.POINTER(FzXattnChain), _P]),
     "fz_gemm_lnout": (C.c_int, [C.POINTER(FzGemmDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int64, _P, _P]),
-    "fz_gemm_ln": (C.c_int, [C.POINTER(FzGemmDesc), C.POINTER(FzGemmLn), _P, _P, _P, _P, _P, _P, _P, _P]),
     "fz_gemm_qkvt": (C.c_int, [C.POINTER(FzGemmDesc), _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P]),
     "fz_gn_epilogue_chunks": (C.c_int, [C.c_int64]),
     "fz_gemm_gn": (C.c_int, [C.POINTER(FzGemmDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, _P]),

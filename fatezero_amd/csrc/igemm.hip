@@ -100,13 +100,6 @@ struct IgArgs {
                           // then the next group (1 = a-tile fastest: consecutive tiles share their B rows; tiles_b = b-tile fastest)
     int tiles_b;
     int nt_flat;          // > 0: split-K launch with a FLAT grid of nt_flat * ksplit workgroups, K slices mapped onto XCDs (ig_launch)
-    // LayerNorm fused around the GEMM (fz_gemm_ln): the B rows are the RAW LayerNorm input, A holds gamma * W
-    const float* ln_in;   // per B row: ln_blocks x (sum, sum of squares) of its 64-channel blocks, or null
-    const float* ln_c1;   // [Ma]: sum_k (gamma W)[a][k]
-    const float* ln_c0;   // [Ma]: sum_k beta_k W[a][k] + bias[a]
-    float ln_eps;
-    int ln_blocks;
-    float* st_out;        // per output row: (Ma / 64) x (sum, sum of squares) of the STORED values, or null
     // fz_gemm_qkvt (the q | k | V^T projection of a self-attention in ONE launch): A rows [vt_split, Ma) are the V projection; the
     // tiles that hold them store TRANSPOSED, yt[row / vt_rows][a - vt_split][row % vt_rows] -- the attention kernels' V^T operand
     half_t* yt;           // [frames][Ma - vt_split][ldyt] or null
@@ -180,13 +173,12 @@ struct IgCfg {
 };
 
 
-// LN: the fz_gemm_ln form (LayerNorm correction of the B rows / row statistics of the output in the epilogue).  Its own
-// instantiation: with the two blocks merely branched around, the 320- and 256-wide tiles of EVERY mode spilled 152-356 VGPRs.
-// VT: the fz_gemm_qkvt form (column tiles at or beyond g.vt_split store transposed).  Its own instantiation for the same reason.
+// VT: the fz_gemm_qkvt form (column tiles at or beyond g.vt_split store transposed).  Its own instantiation: an epilogue block that is
+// merely branched around makes the 320- and 256-wide tiles of every mode spill.
 // GS > 0: the output's GroupNorm statistics (groups of GS channels) leave the epilogue as Welford partials -- the consumer's fz_groupnorm
 // then skips its statistics kernel.  Own instantiations per group width (10 / 20: 320 / 640 channels over 32 groups), so that the
 // statistics pass is straight-line code with its LDS loads in flight together.
-template <int WA, int TA, int WB, int TB, int BK, int NS, int MODE, bool GEGLU, bool LN = false, int PP = 0, bool VT = false, int GS = 0>
+template <int WA, int TA, int WB, int TB, int BK, int NS, int MODE, bool GEGLU, int PP = 0, bool VT = false, int GS = 0>
 FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), (IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::WAVES_PER_SIMD)) igemm_kernel(IgArgs g) {
     typedef IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP> C;
     FZ_DYN_SMEM(raw);
@@ -962,55 +954,6 @@ FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), 
     }
 
     // ---- epilogue ------------------------------------------------------------------------------------------------
-    // LN instantiation: LayerNorm of the B rows applied to the products, y = rstd (x . gamma W - mean c1) + c0 (lane <-> B row),
-    // and the plain bias as its degenerate case (mean 0, rstd 1, c1 0) -- ONE straight-line pass over the accumulators: with a
-    // branch per form the 320 live accumulators merge from two paths and the register allocator spills 150-360 of them.
-    if constexpr (LN) {
-        const bool has_ln = g.ln_in != nullptr;
-        float mu[TB], rs[TB];
-#pragma unroll
-        for (int j = 0; j < TB; ++j) {
-            int64_t px = b0 + (wb * TB + j) * 32 + l31;
-            px = px < g.Nb ? px : g.Nb - 1;
-            const int nblk = has_ln ? g.ln_blocks : 0;
-            const float* sp = g.ln_in + ((int64_t)z * g.Nb + px) * nblk * 2;
-            float s1 = 0.0f, s2 = 0.0f;
-            for (int t = 0; t < nblk; ++t) {  // fixed order: the statistics do not depend on who produced the partials
-                const f32x2 v = *reinterpret_cast<const f32x2*>(sp + 2 * t);
-                s1 += v[0];
-                s2 += v[1];
-            }
-            const float inv_n = 1.0f / (float)(g.ln_blocks * 64);
-            const float m = s1 * inv_n;
-            const float var = fmaxf(s2 * inv_n - m * m, 0.0f);
-            mu[j] = has_ln ? m : 0.0f;
-            rs[j] = has_ln ? fz_rsqrt(var + g.ln_eps) : 1.0f;
-        }
-        const float* zf = reinterpret_cast<const float*>(fz_zero_page);
-        const float* c1p = has_ln ? g.ln_c1 : zf;
-        const float* c0p = has_ln ? g.ln_c0 : zf;
-        const half_t* bp = (!has_ln && g.bias != nullptr) ? g.bias : fz_zero_page;
-        const int ma_f = has_ln ? g.Ma : 0, ma_b = (!has_ln && g.bias != nullptr) ? g.Ma : 0;
-#pragma unroll
-        for (int i = 0; i < TA; ++i)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int co = a0 + (wa * TA + i) * 32 + 8 * gq + 4 * hi;  // Ma % 4 == 0 on this path: whole groups of 4
-                const int cf = co < ma_f ? co : 0, cb = co < ma_b ? co : 0;  // absent / out of range -> the zero page's first words
-                const f32x4 c1 = *reinterpret_cast<const f32x4*>(c1p + cf);
-                f32x4 c0 = *reinterpret_cast<const f32x4*>(c0p + cf);
-                const half4_t bv = *reinterpret_cast<const half4_t*>(bp + cb);
-                const bool live_f = co < ma_f, live_b = co < ma_b;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c0[e] = (live_f ? c0[e] : 0.0f) + (live_b ? (float)bv[e] : 0.0f);
-#pragma unroll
-                for (int j = 0; j < TB; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        acc[i][j][4 * gq + e] = rs[j] * (acc[i][j][4 * gq + e] - (live_f ? mu[j] * c1[e] : 0.0f)) + c0[e];
-                FZ_SCHED_FENCE();  // keeps the TA x 4 coefficient loads from being issued up front (160 VGPRs next to the accumulators)
-            }
-    } else
     // bias in fp32 on the accumulators (lane <-> B row, register group gq <-> 4 consecutive A rows 8*gq + 4*hi)
     if (g.bias != nullptr) {
 #pragma unroll
@@ -1138,57 +1081,6 @@ FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), 
             }
         }
         __syncthreads();
-        if (LN && g.st_out != nullptr) {
-            // Row statistics of what is stored (the next LayerNorm's input): 8 lanes per row, one 64-column block per
-            // iteration, the block's sum / sum of squares reduced over the 8 lanes in a fixed order -> one partial per
-            // (row, 64-column block), independent of the tile shape.  (launcher: plain epilogue, vector path, Ma % 64 == 0)
-            constexpr int NBLK = C::CW / 64;
-            for (int rb = wave; rb * 8 < C::RP; rb += C::NW) {
-                const int pl = rb * 8 + (lane >> 3);
-                const int64_t px = b0 + ps * C::RP + pl;
-                const bool rowok = px < g.Nb;
-                const int64_t pxc = rowok ? px : g.Nb - 1;
-                for (int blk = 0; blk < NBLK; ++blk) {
-                    const int ch = blk * 8 + (lane & 7);
-                    const int co = o0 + ch * 8;
-                    const bool ok = rowok && co < g.Ma;
-                    const int coc = co < g.Ma ? co : 0;
-                    const half8_t v = fz_ld_h8(Cs + pl * C::CSTR + ch * 8);
-                    float f[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-                    if (R1 != nullptr) {
-                        const half8_t r = fz_ld_h8(R1 + pxc * g.ldres + coc);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) f[e] += (float)r[e];
-                    }
-                    if (R2 != nullptr) {
-                        const half8_t r = fz_ld_h8(R2 + pxc * g.ldres + coc);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) f[e] += (float)r[e];
-                    }
-                    half8_t o;
-                    float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        o[e] = (half_t)f[e];
-                        const float fr = (float)o[e];  // statistics of the rounded value the consumer will read
-                        s1 += fr;
-                        s2 += fr * fr;
-                    }
-                    if (ok) fz_st_h8(Y + px * g.ldy + co, o);
-                    if (!ok) s1 = s2 = 0.0f;
-                    s1 = fz_sum8(s1);
-                    s2 = fz_sum8(s2);
-                    if ((lane & 7) == 0 && ok) {
-                        float* sp = g.st_out + (((int64_t)z * g.Nb + px) * (g.Ma / 64) + (o0 / 64 + blk)) * 2;
-                        sp[0] = s1;
-                        sp[1] = s2;
-                    }
-                }
-            }
-            continue;
-        }
         for (int id = tid; id < C::RP * OCH; id += C::T) {
             const int pl = id / OCH, ch = id - pl * OCH;
             const int64_t px = b0 + ps * C::RP + pl;
@@ -1454,7 +1346,7 @@ FZ_KERNEL void __launch_bounds__(256) conv3x3_small_cin_kernel(IgArgs g) {
 // ---------------------------------------------------------------------------------------------------------------
 //                                                   host side
 // ---------------------------------------------------------------------------------------------------------------
-template <int WA, int TA, int WB, int TB, int BK, int NS, int MODE, bool GEGLU, bool LN = false, int PP = 0, bool VT = false, int GS = 0>
+template <int WA, int TA, int WB, int TB, int BK, int NS, int MODE, bool GEGLU, int PP = 0, bool VT = false, int GS = 0>
 static int ig_launch(IgArgs g, int batch, void* stream) {
     typedef IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP> C;
     g.kchunks = fz_ceil_div(g.Cin, BK);
@@ -1471,7 +1363,7 @@ static int ig_launch(IgArgs g, int batch, void* stream) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
     if (dev >= 64 || !(attr_set_mask.load(std::memory_order_relaxed) >> dev & 1)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, LN, PP, VT, GS>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, PP, VT, GS>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return FZ_ERR_LAUNCH;
         if (dev < 64) attr_set_mask.fetch_or(1ull << dev, std::memory_order_relaxed);
@@ -1530,7 +1422,7 @@ static int ig_launch(IgArgs g, int batch, void* stream) {
         static_assert((C::RP * C::CSTR + 2 * 3 * 16 * (C::CW / GS)) <= C::LDS_HALVES, "GroupNorm-statistics scratch does not fit");
         static_assert(C::RP == 128, "the partials' chunk is 128 rows whatever the tile");
     }
-    FZ_LAUNCH((igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, LN, PP, VT, GS>), grid, block, lds, stream, g);
+    FZ_LAUNCH((igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, PP, VT, GS>), grid, block, lds, stream, g);
     return fz_last_launch_status();
 }
 
@@ -1554,53 +1446,52 @@ static int ig_launch(IgArgs g, int batch, void* stream) {
 //   224223: 128 x 256, 8 waves, 3-deep;  222222: 128 x 128, 4 waves, two workgroups per CU
 //   224212: 128 x 256, 8 waves, K step 32, 2-deep: TWO workgroups per CU -- the short-K GEGLU launches (rule in ig_run)
 //   212222:  64 x 128, 4 waves, three workgroups per CU -- small launches and ragged widths
-template <int MODE, bool GEGLU, bool LN = false>
+template <int MODE, bool GEGLU>
 static int ig_dispatch_cfg(int cfg, const IgArgs& g, int batch, void* stream) {
-    if constexpr (!LN) {  // ping-pong K loop (last digit 8): K step 32, 4-slot ring, two wave groups half a phase apart
-        constexpr int P = FZ_PP_ON | FZ_PP_PREP_IN_R;  // the form that measured best (profiles/r03_igemm_ab_v3.txt)
-        if (cfg == 244218) return ig_launch<2, 4, 4, 2, 32, 4, MODE, GEGLU, false, P>(g, batch, stream);
-        if (!GEGLU) {
-            switch (cfg) {
-                case 254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, false, P>(g, batch, stream);
-                default: break;
-            }
+    // ping-pong K loop (last digit 8): K step 32, 4-slot ring, two wave groups half a phase apart
+    constexpr int P = FZ_PP_ON | FZ_PP_PREP_IN_R;  // the form that measured best (profiles/r03_igemm_ab_v3.txt)
+    if (cfg == 244218) return ig_launch<2, 4, 4, 2, 32, 4, MODE, GEGLU, P>(g, batch, stream);
+    if (!GEGLU) {
+        switch (cfg) {
+            case 254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, P>(g, batch, stream);
+            default: break;
         }
-        if constexpr (MODE == 0 && GEGLU) {  // 128 x 256, K step 32, 2-deep ring: two workgroups per CU (the short-K GEGLU launches)
-            if (cfg == 224212) return ig_launch<2, 2, 4, 2, 32, 2, MODE, true, false>(g, batch, stream);
-        }
-#ifdef FZ_IGEMM_TRIALS  // trial forms: tile id + 1000000 * n
-        if constexpr (MODE == 0) {  // two workgroups per CU (K step 32, 2-deep ring, <= 80 accumulator registers)
-            switch (cfg) {
-                case 244112: return ig_launch<2, 4, 4, 1, 32, 2, MODE, GEGLU, false>(g, batch, stream);  // 256 x 128
-                case 224212: return ig_launch<2, 2, 4, 2, 32, 2, MODE, GEGLU, false>(g, batch, stream);  // 128 x 256
-                case 224112: return ig_launch<2, 2, 4, 1, 32, 2, MODE, GEGLU, false>(g, batch, stream);  // 128 x 128
-                default: break;
-            }
-            if (!GEGLU && cfg == 254112) return ig_launch<2, 5, 4, 1, 32, 2, MODE, false, false>(g, batch, stream);  // 320 x 128
-        }
-        if (!GEGLU && MODE != 2) {
-            constexpr int P = FZ_PP_ON | FZ_PP_PREP_IN_R;
-            switch (cfg) {
-                case 254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, false, P>(g, batch, stream);   // one B-side tile per wave:
-                case 158118: return ig_launch<1, 5, 8, 1, 32, 4, MODE, false, false, P>(g, batch, stream);   // slower than their ring twins
-                case 1254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, false, 1>(g, batch, stream);          // prep inside the MFMA cluster
-                case 2254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, false, 1 | 8 | 2>(g, batch, stream);  // no s_setprio
-                case 3254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, false, 1 | 8 | 4>(g, batch, stream);  // groups not staggered
-                case 1254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, false, 1>(g, batch, stream);
-                case 1244218: return ig_launch<2, 4, 4, 2, 32, 4, MODE, false, false, 1>(g, batch, stream);
-                case 4254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, false, 1 | 16>(g, batch, stream);     // K-32 phases
-                case 4244218: return ig_launch<2, 4, 4, 2, 32, 4, MODE, false, false, 1 | 16>(g, batch, stream);
-                case 4254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, false, 1 | 16>(g, batch, stream);
-                case 4158118: return ig_launch<1, 5, 8, 1, 32, 4, MODE, false, false, 1 | 16>(g, batch, stream);
-                default: break;
-            }
-        }
-#endif
     }
+    if constexpr (MODE == 0 && GEGLU) {  // 128 x 256, K step 32, 2-deep ring: two workgroups per CU (the short-K GEGLU launches)
+        if (cfg == 224212) return ig_launch<2, 2, 4, 2, 32, 2, MODE, true>(g, batch, stream);
+    }
+#ifdef FZ_IGEMM_TRIALS  // trial forms: tile id + 1000000 * n
+    if constexpr (MODE == 0) {  // two workgroups per CU (K step 32, 2-deep ring, <= 80 accumulator registers)
+        switch (cfg) {
+            case 244112: return ig_launch<2, 4, 4, 1, 32, 2, MODE, GEGLU>(g, batch, stream);  // 256 x 128
+            case 224212: return ig_launch<2, 2, 4, 2, 32, 2, MODE, GEGLU>(g, batch, stream);  // 128 x 256
+            case 224112: return ig_launch<2, 2, 4, 1, 32, 2, MODE, GEGLU>(g, batch, stream);  // 128 x 128
+            default: break;
+        }
+        if (!GEGLU && cfg == 254112) return ig_launch<2, 5, 4, 1, 32, 2, MODE, false>(g, batch, stream);  // 320 x 128
+    }
+    if (!GEGLU && MODE != 2) {
+        constexpr int P = FZ_PP_ON | FZ_PP_PREP_IN_R;
+        switch (cfg) {
+            case 254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, P>(g, batch, stream);   // one B-side tile per wave:
+            case 158118: return ig_launch<1, 5, 8, 1, 32, 4, MODE, false, P>(g, batch, stream);   // slower than their ring twins
+            case 1254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, 1>(g, batch, stream);          // prep inside the MFMA cluster
+            case 2254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, 1 | 8 | 2>(g, batch, stream);  // no s_setprio
+            case 3254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, 1 | 8 | 4>(g, batch, stream);  // groups not staggered
+            case 1254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, 1>(g, batch, stream);
+            case 1244218: return ig_launch<2, 4, 4, 2, 32, 4, MODE, false, 1>(g, batch, stream);
+            case 4254218: return ig_launch<2, 5, 4, 2, 32, 4, MODE, false, 1 | 16>(g, batch, stream);     // K-32 phases
+            case 4244218: return ig_launch<2, 4, 4, 2, 32, 4, MODE, false, 1 | 16>(g, batch, stream);
+            case 4254118: return ig_launch<2, 5, 4, 1, 32, 4, MODE, false, 1 | 16>(g, batch, stream);
+            case 4158118: return ig_launch<1, 5, 8, 1, 32, 4, MODE, false, 1 | 16>(g, batch, stream);
+            default: break;
+        }
+    }
+#endif
     switch (cfg) {
-        case 244222: return ig_launch<2, 4, 4, 2, 64, 2, MODE, GEGLU, LN>(g, batch, stream);
-        case 224223: return ig_launch<2, 2, 4, 2, 64, 3, MODE, GEGLU, LN>(g, batch, stream);
-        case 222222: return ig_launch<2, 2, 2, 2, 64, 2, MODE, GEGLU, LN>(g, batch, stream);
+        case 244222: return ig_launch<2, 4, 4, 2, 64, 2, MODE, GEGLU>(g, batch, stream);
+        case 224223: return ig_launch<2, 2, 4, 2, 64, 3, MODE, GEGLU>(g, batch, stream);
+        case 222222: return ig_launch<2, 2, 2, 2, 64, 2, MODE, GEGLU>(g, batch, stream);
         default: break;
     }
     if (!GEGLU) {  // odd TA / TA = 1 cannot pair (h, gate) tiles
@@ -1608,26 +1499,21 @@ static int ig_dispatch_cfg(int cfg, const IgArgs& g, int batch, void* stream) {
         // 160 x 128, 4 waves, two workgroups per CU, for the rank-160 down projection of the temporal LoRA pair at 8 frames (128 tiles of
         // 160 x 256 = half the chip): 22 us against 26 us for 158122 on the 64^2 shape, but the 64 x 128 tile the chooser already takes
         // there runs 21 us (profiles/r04_tile_154122_ab.txt): nothing to gain, not shipped
-        if constexpr (!LN) {
-            if (cfg == 154122) return ig_launch<1, 5, 4, 1, 64, 2, MODE, false, false>(g, batch, stream);
-        }
+        if (cfg == 154122) return ig_launch<1, 5, 4, 1, 64, 2, MODE, false>(g, batch, stream);
         // 320 x 128 as 5 x 2 waves of 2 x 2 MFMA tiles (TEN waves: 4 MFMAs per 4 fragment reads per k sub-step instead of 5 per 6, 2.5 waves
         // per SIMD): 3-11 % SLOWER than the 8-wave 5 x 1 form on every conv / projection it carries (profiles/r04_tile_10wave_ab.txt)
-        if constexpr (!LN) {
-            if (cfg == 522222) return ig_launch<5, 2, 2, 2, 64, 2, MODE, false, false>(g, batch, stream);
-        }
+        if (cfg == 522222) return ig_launch<5, 2, 2, 2, 64, 2, MODE, false>(g, batch, stream);
 #endif
-        if constexpr (!LN) {  // 320 x 128 as TWO K groups of 2 x 2 waves of 5 x 2 MFMA tiles (IgCfg::KG): the LDS-lean form of 254122
-            if (cfg == 252222) return ig_launch<2, 5, 2, 2, 64, 2, MODE, false, false, FZ_KG2>(g, batch, stream);
-            if (cfg == 252218) return ig_launch<2, 5, 2, 2, 32, 4, MODE, false, false, FZ_KG2 | FZ_KGPP>(g, batch, stream);  // ... in ping-pong
-            if (cfg == 252214) return ig_launch<2, 5, 2, 2, 32, 4, MODE, false, false, FZ_LC>(g, batch, stream);  // 4 consumer + 4 loader waves
-            if (cfg == 252226) return ig_launch<2, 5, 2, 2, 64, 2, MODE, false, false, FZ_KG2 | FZ_KGSPREAD>(g, batch, stream);  // ... DMA pieces spread
-        }
+        // 320 x 128 as TWO K groups of 2 x 2 waves of 5 x 2 MFMA tiles (IgCfg::KG): the LDS-lean form of 254122
+        if (cfg == 252222) return ig_launch<2, 5, 2, 2, 64, 2, MODE, false, FZ_KG2>(g, batch, stream);
+        if (cfg == 252218) return ig_launch<2, 5, 2, 2, 32, 4, MODE, false, FZ_KG2 | FZ_KGPP>(g, batch, stream);  // ... in ping-pong
+        if (cfg == 252214) return ig_launch<2, 5, 2, 2, 32, 4, MODE, false, FZ_LC>(g, batch, stream);  // 4 consumer + 4 loader waves
+        if (cfg == 252226) return ig_launch<2, 5, 2, 2, 64, 2, MODE, false, FZ_KG2 | FZ_KGSPREAD>(g, batch, stream);  // ... DMA pieces spread
         switch (cfg) {
-            case 254222: return ig_launch<2, 5, 4, 2, 64, 2, MODE, false, LN>(g, batch, stream);
-            case 254122: return ig_launch<2, 5, 4, 1, 64, 2, MODE, false, LN>(g, batch, stream);
-            case 158122: return ig_launch<1, 5, 8, 1, 64, 2, MODE, false, LN>(g, batch, stream);
-            case 212222: return ig_launch<2, 1, 2, 2, 64, 2, MODE, false, LN>(g, batch, stream);
+            case 254222: return ig_launch<2, 5, 4, 2, 64, 2, MODE, false>(g, batch, stream);
+            case 254122: return ig_launch<2, 5, 4, 1, 64, 2, MODE, false>(g, batch, stream);
+            case 158122: return ig_launch<1, 5, 8, 1, 64, 2, MODE, false>(g, batch, stream);
+            case 212222: return ig_launch<2, 1, 2, 2, 64, 2, MODE, false>(g, batch, stream);
             default: break;
         }
     }
@@ -1638,11 +1524,11 @@ static int ig_dispatch_cfg(int cfg, const IgArgs& g, int batch, void* stream) {
 // 1280, 2560; 128 and 64 likewise), so that no column tile straddles the k | v boundary.
 static int ig_dispatch_vt(int cfg, const IgArgs& g, int batch, void* stream) {
     switch (cfg) {
-        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, 0, false, false, 0, true>(g, batch, stream);
-        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, 0, false, false, 0, true>(g, batch, stream);
-        case 224223: return ig_launch<2, 2, 4, 2, 64, 3, 0, false, false, 0, true>(g, batch, stream);
-        case 222222: return ig_launch<2, 2, 2, 2, 64, 2, 0, false, false, 0, true>(g, batch, stream);
-        case 212222: return ig_launch<2, 1, 2, 2, 64, 2, 0, false, false, 0, true>(g, batch, stream);
+        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, 0, false, 0, true>(g, batch, stream);
+        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, 0, false, 0, true>(g, batch, stream);
+        case 224223: return ig_launch<2, 2, 4, 2, 64, 3, 0, false, 0, true>(g, batch, stream);
+        case 222222: return ig_launch<2, 2, 2, 2, 64, 2, 0, false, 0, true>(g, batch, stream);
+        case 212222: return ig_launch<2, 1, 2, 2, 64, 2, 0, false, 0, true>(g, batch, stream);
         default: return FZ_ERR_BAD_ARG;
     }
 }
@@ -1653,8 +1539,8 @@ static int ig_dispatch_vt(int cfg, const IgArgs& g, int batch, void* stream) {
 template <int MODE, int CPG>
 static int ig_dispatch_gs_w(int cfg, const IgArgs& g, int batch, void* stream) {
     switch (cfg) {
-        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, MODE, false, false, 0, false, CPG>(g, batch, stream);
-        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, MODE, false, false, 0, false, CPG>(g, batch, stream);
+        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, MODE, false, 0, false, CPG>(g, batch, stream);
+        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, MODE, false, 0, false, CPG>(g, batch, stream);
         default: return FZ_ERR_BAD_ARG;
     }
 }
@@ -1662,9 +1548,9 @@ static int ig_dispatch_gs_w(int cfg, const IgArgs& g, int batch, void* stream) {
 static int ig_dispatch_lno(int cfg, const IgArgs& g, int batch, void* stream) {
     constexpr int P = FZ_PP_ON | FZ_PP_PREP_IN_R;
     switch (cfg) {
-        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, 0, false, false, 0, false, -1>(g, batch, stream);
-        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, 0, false, false, 0, false, -1>(g, batch, stream);
-        case 254218: return ig_launch<2, 5, 4, 2, 32, 4, 0, false, false, P, false, -1>(g, batch, stream);
+        case 254222: return ig_launch<2, 5, 4, 2, 64, 2, 0, false, 0, false, -1>(g, batch, stream);
+        case 254122: return ig_launch<2, 5, 4, 1, 64, 2, 0, false, 0, false, -1>(g, batch, stream);
+        case 254218: return ig_launch<2, 5, 4, 2, 32, 4, 0, false, P, false, -1>(g, batch, stream);
         default: return FZ_ERR_BAD_ARG;
     }
 }
@@ -1718,13 +1604,12 @@ static void ig_choose(const IgArgs& g, int batch, bool geglu, int64_t ws_floats,
                                 (double)g.Ma * g.Cin * g.taps) * batch;
     for (const IgTile& t : kTiles) {
         if (geglu && !t.geglu_ok) continue;
-        if (g.st_out != nullptr && (t.ba % 64)) continue;  // row statistics are per 64-column block
         if (g.yt != nullptr && (g.vt_split % t.ba || t.cfg == 244222 || t.cfg == 158122)) continue;  // no tile across the k | v boundary
         const int nkt = g.taps * fz_ceil_div(g.Cin, t.bk);
         const int64_t tiles = (int64_t)fz_ceil_div(g.Ma, t.ba) * ((g.Nb + t.bb - 1) / t.bb) * batch;
         const double t_step = 2.0 * t.ba * t.bb * t.bk * t.wg_per_cu / (t.rate_pf * 1e15 / 256.0) * 1e6;  // microseconds
         for (int sk = 1; sk <= 32; sk *= 2) {
-            if (sk > 1 && (geglu || g.ln_in != nullptr || g.yt != nullptr || g.Ma % 4 || g.Ma_store != g.Ma || nkt / sk < 4 || out_elems * sk > (double)ws_floats)) break;
+            if (sk > 1 && (geglu || g.yt != nullptr || g.Ma % 4 || g.Ma_store != g.Ma || nkt / sk < 4 || out_elems * sk > (double)ws_floats)) break;
             const int64_t wgs = tiles * sk;
             const int64_t slots = 256 * t.wg_per_cu;
             const int64_t rounds = (wgs + slots - 1) / slots;
@@ -1752,16 +1637,15 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
         // The two 8-wave tiles whose waves own 2 B-side MFMA tiles run the ping-pong K loop where it measured faster than the ring loop
         // of the same tile on MI355X (profiles/r03_igemm_prod_ring_vs_pp_v3.txt, r03_igemm_ab_v*.txt): no split-K (the loop's three-tile
         // prologue is not amortised over a short K slice: 8^2 convs lost 35 %), K >= 640 (shorter loops are epilogue / HBM-bound either
-        // way), no ragged K, not the LayerNorm-fused form.  +2 ... +7 % on the 16-frame 64^2 convs, +4 ... +16 % on the GEGLU and long-K
+        // way), no ragged K.  +2 ... +7 % on the 16-frame 64^2 convs, +4 ... +16 % on the GEGLU and long-K
         // projections.  The 320 x 128 / 160 x 256 tiles (one B-side MFMA tile per wave: five MFMAs per phase against six fragment
         // reads) measured 3-7 % SLOWER in ping-pong form and stay on the ring loop.
         // (under split-K only when a K slice keeps >= 16 K-64 steps: +1.5 ... +5 % on the 1920 / 2560-wide 16^2 and 32^2 convs,
         //  profiles/r03_igemm_prod_pp_under_splitk.txt; the 8^2 convs with their 5-11-step slices lost 35 %)
         const int64_t k64_per_slice = (int64_t)g.taps * g.Cin / 64 / ksplit;
-        bool pp_ok = g.Cin % 32 == 0 && g.ln_in == nullptr && g.st_out == nullptr && g.yt == nullptr && (int64_t)g.taps * g.Cin >= 640 &&
-                     (ksplit == 1 || k64_per_slice >= 16);
+        bool pp_ok = g.Cin % 32 == 0 && g.yt == nullptr && (int64_t)g.taps * g.Cin >= 640 && (ksplit == 1 || k64_per_slice >= 16);
 #ifdef FZ_IGEMM_TRIALS  // scripts/igemm_timeline.hip: A/B of the library's own choice with / without the substitution, and under split-K
-        if (fz_igemm_trial_pp_splitk_min > 0 && ksplit > 1 && g.Cin % 32 == 0 && g.ln_in == nullptr && g.st_out == nullptr &&
+        if (fz_igemm_trial_pp_splitk_min > 0 && ksplit > 1 && g.Cin % 32 == 0 &&
             (int64_t)g.taps * g.Cin / 64 / ksplit >= fz_igemm_trial_pp_splitk_min)
             pp_ok = true;
         if (fz_igemm_trial_no_pp) pp_ok = false;
@@ -1785,18 +1669,17 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
         // GEGLU with a short K: the epilogue (64 gelu per lane) is longer than the K loop, and with one 8-wave workgroup per CU nothing
         // runs under it.  The 128 x 256 tile fits a CU twice; same-process A/B on MI355X (profiles/r03_igemm_shortk_two_wg_per_cu.txt):
         // 32768 / 65536 x 320 -> 2560: +6 / +10 %, 8192 x 640 -> 5120: +5 % (16384 rows: -2 %, K = 1280: -3 ... -20 %) -- exactly those.
-        if (GEGLU && MODE == 0 && g.ln_in == nullptr && g.st_out == nullptr && ksplit == 1 && cfg != 0 &&
+        if (GEGLU && MODE == 0 && ksplit == 1 && cfg != 0 &&
             ((g.Cin == 320 && g.Nb >= 32768) || (g.Cin == 640 && g.Nb >= 4096 && g.Nb <= 8192)))
             cfg = 224212;
     }
     if (ksplit == 0) ksplit = 1;
-    if (g.ln_in != nullptr) ksplit = 1;  // the LayerNorm correction lives in the GEMM's own epilogue
     bool gs_dropped = false;
     if (g.lno_y != nullptr) {
         // the LayerNorm leaves the epilogue only where the launch the library would pick ANYWAY is a 320-wide tile that IS the whole row
         const bool ok = MODE == 0 && !GEGLU && ksplit == 1 && (cfg == 254222 || cfg == 254122 || cfg == 254218) && g.Ma == 320 &&
-                        g.ln_in == nullptr && g.st_out == nullptr && g.yt == nullptr && g.gs_out == nullptr && batch == 1 &&
-                        (g.ldy % 8) == 0 && (g.ldres % 8) == 0 && (g.lno_ld % 8) == 0;
+                        g.yt == nullptr && g.gs_out == nullptr && batch == 1 && (g.ldy % 8) == 0 && (g.ldres % 8) == 0 &&
+                        (g.lno_ld % 8) == 0;
         if (ok) {
             g.ksplit = 1;
             g.part = nullptr;
@@ -1811,8 +1694,8 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
         // Statistics leave the epilogue only where the launch the library would pick ANYWAY is a 320-wide ring tile without split-K
         // (forcing such a tile onto a launch that wants another one costs more than the statistics kernel it saves): otherwise the
         // launch runs as usual and the caller is told to compute the statistics itself (FZ_GEMM_NO_STATS).
-        const bool ok = (MODE == 0 || MODE == 2) && !GEGLU && ksplit == 1 && (cfg == 254222 || cfg == 254122) && g.ln_in == nullptr &&
-                        g.st_out == nullptr && g.yt == nullptr && batch == 1;
+        const bool ok = (MODE == 0 || MODE == 2) && !GEGLU && ksplit == 1 && (cfg == 254222 || cfg == 254122) && g.yt == nullptr &&
+                        batch == 1;
         if (ok) {
             g.ksplit = 1;
             g.part = nullptr;
@@ -1822,15 +1705,10 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
         gs_dropped = true;
     }
     if (g.yt != nullptr) {               // fz_gemm_qkvt: transposed tiles leave from the GEMM's own epilogue as well
-        if (GEGLU || MODE != 0 || ksplit != 1 || g.ln_in != nullptr || g.st_out != nullptr) return FZ_ERR_UNSUPPORTED;
+        if (GEGLU || MODE != 0 || ksplit != 1) return FZ_ERR_UNSUPPORTED;
         g.ksplit = 1;
         g.part = nullptr;
         return ig_dispatch_vt(cfg, g, batch, stream);
-    }
-    bool stats_dropped = false;
-    if (g.st_out != nullptr && ksplit > 1) {  // the split-K tail does not compute row statistics: tell the caller
-        g.st_out = nullptr;
-        stats_dropped = true;
     }
     g.ksplit = ksplit;
     g.part = nullptr;
@@ -1839,20 +1717,13 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
         if ((int64_t)ksplit * batch * g.Nb * g.Ma > workspace_floats) return FZ_ERR_BAD_ARG;
         g.part = workspace;
     }
-    int rc;
-    if constexpr (MODE == 0) {
-        rc = (g.ln_in != nullptr || g.st_out != nullptr) ? ig_dispatch_cfg<0, GEGLU, true>(cfg, g, batch, stream)
-                                                         : ig_dispatch_cfg<0, GEGLU>(cfg, g, batch, stream);
-    } else {
-        if (g.ln_in != nullptr || g.st_out != nullptr) return FZ_ERR_UNSUPPORTED;
-        rc = ig_dispatch_cfg<MODE, GEGLU>(cfg, g, batch, stream);
-    }
+    const int rc = ig_dispatch_cfg<MODE, GEGLU>(cfg, g, batch, stream);
     if (rc != FZ_OK || ksplit == 1) return rc != FZ_OK ? rc : (gs_dropped ? FZ_GEMM_NO_STATS : FZ_OK);
     const int64_t rblocks = (g.Nb * batch + 3) / 4;   // one wave per row, 4 rows per workgroup
     dim3 grid((unsigned)(rblocks < 16384 ? rblocks : 16384), (unsigned)((g.Ma / 4 + 63) / 64)), block(256);
     FZ_LAUNCH(igemm_reduce_kernel, grid, block, 0, stream, g, batch);
     const int rc2 = fz_last_launch_status();
-    return rc2 != FZ_OK ? rc2 : ((stats_dropped || gs_dropped) ? FZ_GEMM_NO_STATS : FZ_OK);
+    return rc2 != FZ_OK ? rc2 : (gs_dropped ? FZ_GEMM_NO_STATS : FZ_OK);
 }
 
 extern "C" int64_t fz_gemm_workspace_floats(int64_t rows, int out_features, int batch) {
@@ -1862,22 +1733,8 @@ extern "C" int64_t fz_gemm_workspace_floats(int64_t rows, int out_features, int 
     return 8 * out < cap ? 8 * out : (2 * out < cap ? cap : 2 * out);
 }
 
-static int gemm_impl(const FzGemmDesc* d, const FzGemmLn* ln, const void* x, const void* w, const void* bias, const void* res,
-                     const void* res2, void* y, void* workspace, void* stream);
-
 extern "C" int fz_gemm(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2,
                        void* y, void* workspace, void* stream) {
-    return gemm_impl(d, nullptr, x, w, bias, res, res2, y, workspace, stream);
-}
-
-extern "C" int fz_gemm_ln(const FzGemmDesc* d, const FzGemmLn* ln, const void* x, const void* w, const void* bias, const void* res,
-                          const void* res2, void* y, void* workspace, void* stream) {
-    if (!ln) return FZ_ERR_BAD_ARG;
-    return gemm_impl(d, ln, x, w, bias, res, res2, y, workspace, stream);
-}
-
-static int gemm_impl(const FzGemmDesc* d, const FzGemmLn* ln, const void* x, const void* w, const void* bias, const void* res,
-                     const void* res2, void* y, void* workspace, void* stream) {
     if (!d || !x || !w || !y || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
     const int batch = d->batch > 0 ? d->batch : 1;
     IgArgs g = {};
@@ -1909,22 +1766,6 @@ static int gemm_impl(const FzGemmDesc* d, const FzGemmLn* ln, const void* x, con
         g.bias = (const half_t*)bias;
         const int outw = geglu ? d->out_features / 2 : d->out_features;
         if (d->ldy < outw) return FZ_ERR_BAD_ARG;
-        if (ln != nullptr) {
-            if (ln->stats_in != nullptr) {  // x holds the raw LayerNorm input, w holds gamma * W
-                if (!ln->c1 || !ln->c0 || d->in_features % 64 || d->out_features % 64 || d->x_batch_stride % d->ldx) return FZ_ERR_UNSUPPORTED;
-                g.ln_in = ln->stats_in;
-                g.ln_c1 = ln->c1;
-                g.ln_c0 = ln->c0;
-                g.ln_eps = ln->eps;
-                g.ln_blocks = d->in_features / 64;
-                g.bias = nullptr;  // folded into c0
-            }
-            if (ln->stats_out != nullptr) {
-                if (geglu || d->out_features % 64 || (d->ldy % 8) || (d->y_batch_stride % 8) || (g.ldres % 8) || (g.res_bs % 8))
-                    return FZ_ERR_UNSUPPORTED;
-                g.st_out = ln->stats_out;
-            }
-        }
         if (geglu) {
             if (d->out_features % 64 || res || res2) return FZ_ERR_UNSUPPORTED;
             return ig_run<0, true>(g, batch, d->tile_cfg, 1, nullptr, 0, stream);
@@ -1932,7 +1773,7 @@ static int gemm_impl(const FzGemmDesc* d, const FzGemmLn* ln, const void* x, con
         return ig_run<0, false>(g, batch, d->tile_cfg, d->split_k, (float*)workspace, d->workspace_floats, stream);
     }
     // y[b][out][row] (V^T): A = x rows of the batch element (row index contiguous in the output), B = W rows
-    if (geglu || bias || res || res2 || ln) return FZ_ERR_UNSUPPORTED;
+    if (geglu || bias || res || res2) return FZ_ERR_UNSUPPORTED;
     if (d->rows >= (1ll << 31)) return FZ_ERR_UNSUPPORTED;
     g.a = (const half_t*)x;
     g.lda = d->ldx;

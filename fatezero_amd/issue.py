@@ -147,7 +147,7 @@ def _model_switches():
     """The module-level switches of the model code that change which kernels a forward launches (same-box A/B runs flip them at run time):
     a plan recorded under one setting is not the launch list of another."""
     from .video_diffusion.models import attention as A, lora as Lo, resnet as R
-    return (A.LN_FUSION, A.QKV_FUSION, A.LN_FROM_PRODUCER, R.GN_FROM_EPILOGUE, Lo.LORA_PAIR_FUSION, Lo.LORA_PAIR_GN, Lo.LORA_PAIR_ALWAYS)
+    return (A.QKV_FUSION, A.LN_FROM_PRODUCER, R.GN_FROM_EPILOGUE, Lo.LORA_PAIR_FUSION, Lo.LORA_PAIR_GN, Lo.LORA_PAIR_ALWAYS)
 
 
 class ForwardPlan:

@@ -57,17 +57,10 @@ def _plan_for(controller, is_cross, place, n, clip, heads, lq, lk, device):
     return None  # foreign controller: generic path
 
 
-# LayerNorm folded into the GEMMs around it (fz_gemm_ln: row statistics from the producing out-projection, correction in the
-# consuming projection's epilogue).  Correct and tested (kernel cases on MI355X, the pipeline with the switch on in
-# tests/test_pipeline_emu.py) but OFF: same-box A/B (scripts/ab_bench.py, profiles/r02_ab_ln_fusion.txt) shows the job 1.1-1.3 %
-# SLOWER with it -- the 30 LayerNorm launches it removes per forward (C <= 640 levels) cost less than the statistics loop and the
-# per-row correction add to the 60 GEMM epilogues.
-LN_FUSION = False
 # q | k | V^T of a self-attention in ONE launch (fz_gemm_qkvt: the V columns leave transposed from the same GEMM; the LayerNorm
 # output is read once instead of twice, one launch instead of two) wherever the frame's token count is a multiple of 64 -- every level
 # of a 512^2 clip.  Bit-identical to the two launches (tests/kernel_cases.py: case_gemm_qkvt).  Switch kept for same-box A/B runs.
 QKV_FUSION = os.environ.get("FZ_NO_QKV_FUSION") is None  # (the env switch: same-box A/B runs of bench.py)
-LN_FUSION_MAX_C = 640  # wider rows (K = 1280) want split-K in the consuming GEMM, which the fused epilogue excludes
 # LayerNorm out of the PRODUCING projection's epilogue (fz_gemm_lnout, round 5): every `x = f(norm(x)) + x` step ends in a Linear + residual
 # whose output is the next LayerNorm's input, and at the 320-channel level the 320-wide GEMM tile holds whole rows -- the epilogue computes
 # exact row statistics on the values it stores and writes LN(y) beside y: proj_in -> norm1, attn1.to_out -> norm2, attn2.to_out -> norm3,
@@ -89,29 +82,14 @@ XATTN_CHAIN = os.environ.get("FZ_NO_XATTN_CHAIN") is None
 XATTN_CHAIN_FRONT = os.environ.get("FZ_XATTN_FRONT") is not None  # (the front form measured EQUAL for the job, profiles/r06_xattn_chain_job_ab.txt: opt-in)
 
 
-class Prenormed:
-    """LN(y) that came out of the projection which produced y (fz_gemm_lnout): travels where the row statistics of fz_gemm_ln would."""
-    __slots__ = ("t",)
-
-    def __init__(self, t):
-        self.t = t
-
-
-def _out_proj(lin, out, residual, want_stats, ln_next):
-    """to_out / ff.net[2]: Linear + residual; with `ln_next` (the LayerNorm that consumes the result) also LN(result) from the same launch."""
+def _out_proj(lin, out, residual, ln_next):
+    """to_out / ff.net[2]: Linear + residual -> (y, None); with `ln_next` (the LayerNorm that consumes the result) also LN(y) from the same launch
+    where it can produce it -> (y, LN(y) or None)."""
     if ln_next is not None and out.is_contiguous():
         g, b = ln_next.packed(out.device)
         w, bias = lin.packed(out.dtype, out.device)
-        y, yln = K.gemm_lnout(out, w, bias, (g, b, ln_next.eps), res=residual)
-        return y, (None if yln is None else Prenormed(yln))
-    return lin.apply(out, res=residual, want_stats=want_stats)
-
-
-def _ln_ready(norm, stats, x):
-    """Can the LayerNorm `norm` of x be folded into the Linear that consumes it?  (statistics from the producing GEMM at hand,
-    64-channel blocks, fp16 engine)"""
-    return (LN_FUSION and norm is not None and stats is not None and x.shape[-1] % 64 == 0 and x.shape[-1] <= LN_FUSION_MAX_C
-            and x.dtype == torch.float16)
+        return K.gemm_lnout(out, w, bias, (g, b, ln_next.eps), res=residual)
+    return lin.apply(out, res=residual), None
 
 
 def layer_norm_tokens(norm, x):
@@ -149,7 +127,6 @@ class CrossAttention(nn.Module):
         self._qkv_self = None
         self._ctx_kv = None   # (ctx, its version, K, V^T, fz_xattn_chain's pack of them or None)
         self._xchain = {}     # fz_xattn_chain's packed weights by (device, id of attn1's to_out or None)
-        self._ln_fold = None  # (id of the norm, LnFold): the consuming projection with its LayerNorm folded in
 
     # -- helpers -----------------------------------------------------------------------------------------
     def _qk_weight(self, dtype, device, q_fold=1.0):
@@ -217,9 +194,11 @@ class CrossAttention(nn.Module):
             bo = self.to_out[0].packed(o1.dtype, o1.device)[1]
             y, yln, _ = K.xattn_chain(o1, packed, kvp, bo, res=hs, frames_per_batch=clip, heads=self.heads, lk=ctx.shape[1], scale=self.scale,
                                       ln=(g3, b3, ln_next.eps), front_eps=norm_in.eps)
-            return y, Prenormed(yln)
-        hs1, st = _out_proj(attn1_out, o1, hs, False, norm_in)
-        return self.forward_cross(x.like(hs1), ctx, clip, residual=hs1, norm=norm_in, stats=st, ln_next=ln_next, plan=plan)
+            return y, yln
+        hs1, n_in = _out_proj(attn1_out, o1, hs, norm_in)
+        if n_in is None:
+            n_in = layer_norm_tokens(norm_in, hs1)
+        return self.forward_cross(x.like(n_in), ctx, clip, residual=hs1, ln_next=ln_next, plan=plan)
 
     def _generic_controller_call(self, controller, is_cross, q, k, vt, out, clip, lq, lk_total, run_capture, run_inject):
         """Reference protocol for a controller that only has __call__: materialise P, call it, apply the result.
@@ -236,37 +215,23 @@ class CrossAttention(nn.Module):
         run_inject(p)
 
     # -- cross attention (attention_register.py:71-128) ------------------------------------------------------
-    def forward_cross(self, x: Tokens, ctx, clip: int, residual=None, norm=None, stats=None, want_stats=False, ln_next=None, plan=False):
-        """x.data: hidden states [N, L, C] -- LayerNorm'ed, or RAW together with (`norm`, `stats` = the row sums their producer
-        wrote): the LayerNorm then rides in the to_q GEMM (fz_gemm_ln); ctx: [B, 77, Dctx] fp16.  Returns residual +
-        to_out(attention) (the block's `hidden_states = attn2(...) + hidden_states`, attention.py:303-311, fused into the GEMM
-        epilogue), plus that result's row statistics when want_stats."""
+    def forward_cross(self, x: Tokens, ctx, clip: int, residual=None, ln_next=None, plan=False):
+        """x.data: LayerNorm'ed hidden states [N, L, C]; ctx: [B, 77, Dctx] fp16.  Returns (residual + to_out(attention), LN of that by
+        `ln_next` or None): the block's `hidden_states = attn2(...) + hidden_states`, attention.py:303-311, fused into the GEMM epilogue."""
         n, lq, c = x.data.shape
         ctrl = self.controller
         if plan is False:  # (a plan handed in was already taken from the controller for THIS call: forward_cross_after's fall-back)
-            if (ln_next is not None and residual is not None and residual.is_contiguous() and not want_stats
+            if (ln_next is not None and residual is not None and residual.is_contiguous()
                     and self._chain_applies(n, lq, c, x.data.dtype, ctx)):
                 plan = _plan_for(ctrl, True, self.place_in_unet, n, clip, self.heads, lq, ctx.shape[1], x.data.device)
                 if plan is None or plan.mode == K.FZ_ATTN_FLASH:  # to_q -> cross-attention -> to_out + residual + LayerNorm in one launch
-                    xn = stats.t if isinstance(stats, Prenormed) else (x.data if norm is None else layer_norm_tokens(norm, x.data))
                     _, _, kvp = self._context_kv(ctx, want_pack=True)
+                    xn = x.data.contiguous()
                     g3, b3 = ln_next.packed(xn.device)
-                    y, yln = K.xattn_chain(xn.contiguous(), self._chain_weights(xn.device), kvp, self.to_out[0].packed(xn.dtype, xn.device)[1],
-                                           res=residual, frames_per_batch=clip, heads=self.heads, lk=ctx.shape[1], scale=self.scale,
-                                           ln=(g3, b3, ln_next.eps))
-                    return y, Prenormed(yln)
-        if isinstance(stats, Prenormed):  # LN(x) came out of the producing projection's epilogue
-            q = self.to_q.apply(stats.t)
-        elif norm is not None:
-            if _ln_ready(norm, stats, x.data):
-                if self._ln_fold is None or self._ln_fold[0] is not norm or self._ln_fold[1].w.device != x.data.device:
-                    self._ln_fold = (norm, K.LnFold(self.to_q.weight, self.to_q.bias, norm.weight, norm.bias, norm.eps,
-                                                    x.data.device))
-                q = K.gemm(x.data, None, None, ln=self._ln_fold[1], ln_stats=stats)
-            else:
-                q = self.to_q.apply(layer_norm_tokens(norm, x.data))
-        else:
-            q = self.to_q.apply(x.data)
+                    return K.xattn_chain(xn, self._chain_weights(xn.device), kvp, self.to_out[0].packed(xn.dtype, xn.device)[1],
+                                         res=residual, frames_per_batch=clip, heads=self.heads, lk=ctx.shape[1], scale=self.scale,
+                                         ln=(g3, b3, ln_next.eps))
+        q = self.to_q.apply(x.data)
         kk, vt, _ = self._context_kv(ctx)
         lk = ctx.shape[1]
         out = torch.empty(n, lq, self.inner_dim, dtype=q.dtype, device=q.device)
@@ -292,50 +257,31 @@ class CrossAttention(nn.Module):
             if plan.n_plain < n:
                 K.attn_cross(q, kk, vt, out, mode=plan.mode, frame0=plan.n_plain, n_frames=n - plan.n_plain, p=plan.p,
                              mapper_t=plan.mapper_t, coef=plan.coef, cur_out=plan.cur_out, **kw)
-        return _out_proj(self.to_out[0], out, residual, want_stats, ln_next)
+        return _out_proj(self.to_out[0], out, residual, ln_next)
 
     # -- temporal attention (attention.py:327-337; never controlled, attention_register.py:242) ---------------
-    def forward_temporal(self, x_norm, batch: int, clip: int, residual=None, norm=None, stats=None):
-        """x_norm: [B*F, L, C] LayerNorm'ed -- or RAW with (`norm`, `stats`): the LayerNorm then rides in the fused q/k/v GEMM;
-        attention over the F frames of every (b, token); + residual in the epilogue."""
+    def forward_temporal(self, x_norm, batch: int, clip: int, residual=None):
+        """x_norm: [B*F, L, C] LayerNorm'ed; attention over the F frames of every (b, token); + residual in the epilogue."""
         n, l, c = x_norm.shape
-        if isinstance(stats, Prenormed):
-            x_norm, norm, stats = stats.t, None, None
-        if norm is not None and not _ln_ready(norm, stats, x_norm):
-            x_norm, norm = layer_norm_tokens(norm, x_norm), None
-        if norm is not None:
-            if self._ln_fold is None or self._ln_fold[0] is not norm or self._ln_fold[1].w.device != x_norm.device:
-                wcat = torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0)
-                self._ln_fold = (norm, K.LnFold(wcat, None, norm.weight, norm.bias, norm.eps, x_norm.device))
-            qkv = K.gemm(x_norm, None, None, ln=self._ln_fold[1], ln_stats=stats)
-        else:
-            if self._qkv is None or self._qkv.device != x_norm.device:
-                self._qkv = torch.cat([self._qk_weight(x_norm.dtype, x_norm.device),
-                                       self.to_v.packed(x_norm.dtype, x_norm.device)[0]], 0).contiguous()
-            shard = D.active_shard()
-            if shard is not None:
-                # frames split over ranks: every pixel attends over ALL frames of the clip.  K | V first, their all-gather POSTED,
-                # then the Q projection -- it runs while RCCL moves the other ranks' K / V (same weights, same arithmetic per
-                # output element as the fused q|k|v GEMM: the rows of the weight matrix are merely projected in two launches)
-                inner = self.inner_dim
-                kv_loc = K.gemm(x_norm, self._qkv[inner:])
-                pend = shard.all_gather_frames_async(kv_loc.reshape(batch, clip, l, 2 * inner), tag="temporal_attn")
-                q = K.gemm(x_norm, self._qkv[:inner])
-                kv = pend.wait().reshape(batch * shard.clip_len, l, 2 * inner)
-                out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
-                K.attn_temporal(q, kv[..., :inner], kv[..., inner:], out, batch=batch, clip_len=clip,
-                                kv_frames=shard.clip_len, heads=self.heads, scale=self.scale)
-                return self.to_out[0].apply(out, res=residual)
-            qkv = K.gemm(x_norm, self._qkv)
+        if self._qkv is None or self._qkv.device != x_norm.device:
+            self._qkv = torch.cat([self._qk_weight(x_norm.dtype, x_norm.device),
+                                   self.to_v.packed(x_norm.dtype, x_norm.device)[0]], 0).contiguous()
         inner = self.inner_dim
-        out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
         shard = D.active_shard()
-        if shard is not None:  # every pixel attends over ALL frames of the clip: gather this layer's K and V
-            kv = shard.all_gather_frames(qkv[..., inner:].reshape(batch, clip, l, 2 * inner))
-            kv = kv.reshape(batch * shard.clip_len, l, 2 * inner)
-            K.attn_temporal(qkv[..., :inner], kv[..., :inner], kv[..., inner:], out, batch=batch, clip_len=clip,
+        if shard is not None:
+            # frames split over ranks: every pixel attends over ALL frames of the clip.  K | V first, their all-gather POSTED,
+            # then the Q projection -- it runs while RCCL moves the other ranks' K / V (same weights, same arithmetic per
+            # output element as the fused q|k|v GEMM: the rows of the weight matrix are merely projected in two launches)
+            kv_loc = K.gemm(x_norm, self._qkv[inner:])
+            pend = shard.all_gather_frames_async(kv_loc.reshape(batch, clip, l, 2 * inner), tag="temporal_attn")
+            q = K.gemm(x_norm, self._qkv[:inner])
+            kv = pend.wait().reshape(batch * shard.clip_len, l, 2 * inner)
+            out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
+            K.attn_temporal(q, kv[..., :inner], kv[..., inner:], out, batch=batch, clip_len=clip,
                             kv_frames=shard.clip_len, heads=self.heads, scale=self.scale)
             return self.to_out[0].apply(out, res=residual)
+        qkv = K.gemm(x_norm, self._qkv)
+        out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
         K.attn_temporal(qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:], out, batch=batch, clip_len=clip,
                         heads=self.heads, scale=self.scale)
         return self.to_out[0].apply(out, res=residual)
@@ -346,7 +292,6 @@ class CrossAttention(nn.Module):
         self._qkv_self = None
         self._ctx_kv = None
         self._xchain = {}
-        self._ln_fold = None
         return super().load_state_dict(*a, **k)
 
 
@@ -391,7 +336,7 @@ class _ShardedKV:
 class SparseCausalAttention(CrossAttention):
     """attention.py:340-422 / attention_register.py:131-218: frame f attends the K/V of frames idx_j(f)."""
 
-    def forward_self(self, x: Tokens, clip: int, index_list, residual=None, want_stats=False, ln_next=None, raw_out=False):
+    def forward_self(self, x: Tokens, clip: int, index_list, residual=None, ln_next=None, raw_out=False):
         n, lq, c = x.data.shape
         xn = x.data
         # head dims with a free MFMA contraction slot (SD-1.x: 40): the softmax scale and log2(e) go into Wq, q comes out of
@@ -454,7 +399,7 @@ class SparseCausalAttention(CrossAttention):
                     K.attn_self(q, kk, vt, out, mode=plan.mode, p=plan.p, **rest, **kw)
         if raw_out:  # the output projection rides in the launch that follows (forward_cross_after)
             return out
-        return _out_proj(self.to_out[0], out, residual, want_stats, ln_next)
+        return _out_proj(self.to_out[0], out, residual, ln_next)
 
 
 class _GEGLU(nn.Module):
@@ -478,7 +423,6 @@ class FeedForward(nn.Module):
     def __init__(self, dim, mult=4):
         super().__init__()
         self.net = nn.ModuleList([_GEGLU(dim, dim * mult), nn.Identity(), _LinearParams(dim * mult, dim)])
-        self._ln_fold = None
         self._chain = None  # (device, fz_ff_chain's packed weight stream, b2)
 
     def _chain_pack(self, device):
@@ -493,40 +437,27 @@ class FeedForward(nn.Module):
 
     def load_state_dict(self, *a, **k):  # the packed stream must follow the parameters
         self._chain = None
-        self._ln_fold = None
         return super().load_state_dict(*a, **k)
 
-    def apply(self, x, res=None, norm=None, stats=None, want_stats=False, ln_next=None):
-        """res + Linear(h * gelu(gate)): the 8C-wide GEGLU intermediate is never written (gate applied in the epilogue of the
-        projection GEMM), the residual add rides in the epilogue of the output GEMM.  x: LayerNorm'ed, or RAW with
-        (`norm`, `stats`) -- the LayerNorm then rides in the projection GEMM as well (fz_gemm_ln)."""
+    def apply(self, x, res=None, ln_next=None):
+        """res + Linear(h * gelu(gate)) of the LayerNorm'ed x: the 8C-wide GEGLU intermediate is never written (gate applied in the epilogue
+        of the projection GEMM), the residual add rides in the epilogue of the output GEMM.  Returns (y, LN of y by `ln_next` or None)."""
         g = self.net[0]
-        fused = g.proj.weight.shape[0] % 64 == 0
-        if isinstance(stats, Prenormed):
-            x, norm, stats = stats.t, None, None
-        if norm is not None and not (fused and _ln_ready(norm, stats, x)):
-            x, norm = layer_norm_tokens(norm, x), None
         inner = g.proj.weight.shape[0] // 2
-        if (FF_CHAIN and norm is None and not want_stats and x.dtype == torch.float16 and x.is_contiguous() and (res is None or res.is_contiguous())
+        if (FF_CHAIN and x.dtype == torch.float16 and x.is_contiguous() and (res is None or res.is_contiguous())
                 and D.active_shard() is None and K.ff_chain_preferred(x.numel() // x.shape[-1], x.shape[-1], inner)):
             packed, b2 = self._chain_pack(x.device)
             ln = None
             if ln_next is not None:
                 gam, bet = ln_next.packed(x.device)
                 ln = (gam, bet, ln_next.eps)
-            y, yln = K.ff_chain(x, packed, b2, inner, res=res, ln=ln)
-            return y, (None if yln is None else Prenormed(yln))
-        if norm is not None:
-            if getattr(self, "_ln_fold", None) is None or self._ln_fold[0] is not norm or self._ln_fold[1].w.device != x.device:
-                self._ln_fold = (norm, K.LnFold(g.proj.weight, g.proj.bias, norm.weight, norm.bias, norm.eps, x.device,
-                                                pack=K.pack_geglu))
-            h = K.gemm(x, None, None, geglu=True, ln=self._ln_fold[1], ln_stats=stats)
-        elif fused:
+            return K.ff_chain(x, packed, b2, inner, res=res, ln=ln)
+        if g.proj.weight.shape[0] % 64 == 0:
             w, b = g.packed(x.dtype, x.device)
             h = K.gemm(x, w, b, geglu=True)
         else:
             h = K.geglu(g.proj.apply(x))
-        return _out_proj(self.net[2], h, res, want_stats, ln_next)
+        return _out_proj(self.net[2], h, res, ln_next)
 
 
 class SpatioTemporalTransformerBlock(nn.Module):
@@ -557,23 +488,25 @@ class SpatioTemporalTransformerBlock(nn.Module):
         hs = x.data
         clip = x.f
         lnp = LN_FROM_PRODUCER and hs.shape[-1] == LN_FROM_PRODUCER_C and hs.dtype == torch.float16 and D.active_shard() is None
-        # every `x = f(norm(x)) + x` of attention.py:295-337 ends in a GEMM: the residual add is that GEMM's epilogue -- and
-        # so are the row statistics of the result, which let norm2 / norm3 / norm_temporal ride inside the GEMM that consumes
-        # them (fz_gemm_ln; `st` is None where that form does not apply and the LayerNorm kernel runs instead).  norm1 stays a
-        # kernel: its output also feeds the transposed V projection.
+        # every `x = f(norm(x)) + x` of attention.py:295-337 ends in a GEMM: the residual add is that GEMM's epilogue -- and at the 320-channel
+        # level so is the LayerNorm that opens the next step (`lnp`; None where the launch cannot produce it and the LayerNorm kernel runs)
         n1 = prenorm1 if prenorm1 is not None else layer_norm_tokens(self.norm1, hs)
-        want = LN_FUSION and hs.shape[-1] <= LN_FUSION_MAX_C
-        if (lnp and XATTN_CHAIN_FRONT and not want and hs.is_contiguous()
+        if (lnp and XATTN_CHAIN_FRONT and hs.is_contiguous()
                 and self.attn2._chain_applies(hs.shape[0], hs.shape[1], hs.shape[2], hs.dtype, ctx)):
             # attn1.to_out + residual + norm2 -> attn2 (to_q, cross-attention, to_out) + residual + norm3: ONE launch behind the self-attention
             o1 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, raw_out=True)
-            hs, st = self.attn2.forward_cross_after(x, o1, self.attn1.to_out[0], hs, self.norm2, ctx, clip, self.norm3)
+            hs, n3 = self.attn2.forward_cross_after(x, o1, self.attn1.to_out[0], hs, self.norm2, ctx, clip, self.norm3)
         else:
-            hs, st = self.attn1.forward_self(x.like(n1), clip, self.sc_index, residual=hs, want_stats=want, ln_next=self.norm2 if lnp else None)
-            hs, st = self.attn2.forward_cross(x.like(hs), ctx, clip, residual=hs, norm=self.norm2, stats=st, want_stats=want,
-                                              ln_next=self.norm3 if lnp else None)
-        hs, st = self.ff.apply(hs, res=hs, norm=self.norm3, stats=st, want_stats=want, ln_next=self.norm_temporal if lnp else None)
-        hs = self.attn_temporal.forward_temporal(hs, x.b, clip, residual=hs, norm=self.norm_temporal, stats=st)
+            hs, n2 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, residual=hs, ln_next=self.norm2 if lnp else None)
+            if n2 is None:
+                n2 = layer_norm_tokens(self.norm2, hs)
+            hs, n3 = self.attn2.forward_cross(x.like(n2), ctx, clip, residual=hs, ln_next=self.norm3 if lnp else None)
+        if n3 is None:
+            n3 = layer_norm_tokens(self.norm3, hs)
+        hs, nt = self.ff.apply(n3, res=hs, ln_next=self.norm_temporal if lnp else None)
+        if nt is None:
+            nt = layer_norm_tokens(self.norm_temporal, hs)
+        hs = self.attn_temporal.forward_temporal(nt, x.b, clip, residual=hs)
         return x.like(hs)
 
 

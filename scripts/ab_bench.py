@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of a module-level switch: runs bench.run_job with the switch on / off, interleaved, and prints job times.
-    python scripts/ab_bench.py fatezero_amd.video_diffusion.models.attention LN_FUSION"""
+    python scripts/ab_bench.py fatezero_amd.video_diffusion.models.attention QKV_FUSION"""
 import importlib
 import os
 import sys

@@ -65,15 +65,6 @@ def test_unet_tiny40_reference_golden_emu():
     assert r["err"] <= 1.5e-2 * r["scale"], r
 
 
-def test_unet_tiny40_layernorm_fusion_emu(monkeypatch):
-    # same vector with LayerNorm folded into the surrounding GEMMs (fz_gemm_ln; off by default, attention.py LN_FUSION)
-    from fatezero_amd.video_diffusion.models import attention as A
-    monkeypatch.setattr(A, "LN_FUSION", True)
-    r = PC.run_unet_golden("unet_tiny40_default", "cpu")
-    print(r)
-    assert r["err"] <= 1.5e-2 * r["scale"], r
-
-
 @pytest.mark.skipif(__import__("os").environ.get("FZ_FULL_PARITY") != "1", reason="5 minutes of emulation: opt in with FZ_FULL_PARITY=1")
 def test_whole_job_with_every_window_toggling_mini_emu():
     """(opt-in) The harness of the long-clip / window-transition cases (pipeline_cases.run_geometry_case: cfg3 / cfg4 / cfg5 / full-width cfg2 on
