@@ -57,7 +57,7 @@ class FzGemmDesc(C.Structure):
         ("batch", C.c_int32), ("epilogue", C.c_int32),
         ("x_batch_stride", C.c_int64), ("y_batch_stride", C.c_int64), ("res_batch_stride", C.c_int64),
         ("transpose_out", C.c_int32), ("tile_cfg", C.c_int32), ("split_k", C.c_int32), ("reserved0", C.c_int32),
-        ("workspace_floats", C.c_int64), ("w_batch_stride", C.c_int64),
+        ("workspace_floats", C.c_int64), ("w_batch_stride", C.c_int64), ("res_rows", C.c_int64),
     ]
 
 
@@ -69,6 +69,7 @@ class FzXattnChain(C.Structure):
         ("rows", C.c_int64), ("rows_per_frame", C.c_int64),
         ("frames_per_batch", C.c_int32), ("channels", C.c_int32), ("heads", C.c_int32), ("lk", C.c_int32),
         ("scale", C.c_float), ("ln_eps", C.c_float), ("ln1_eps", C.c_float), ("front", C.c_int32),
+        ("in_frames", C.c_int32), ("reserved0", C.c_int32),
     ]
 
 
@@ -111,7 +112,7 @@ _SIGS = {
     "fz_groupnorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                _P, _P]),
     "fz_groupnorm_cat": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
-                                   _P, _P]),
+                                   _P, C.c_int, _P]),
     "fz_groupnorm_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "fz_groupnorm_apply": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P,
                                      C.c_int, C.c_int, _P, _P]),
@@ -135,6 +136,7 @@ _SIGS = {
     "fz_transpose_pad": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P]),
     "fz_latent_update": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, C.c_int, C.c_int, _P]),
     "fz_accumulate": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "fz_repeat": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "fz_peer_put": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_uint32, _P, _P]),
     "fz_peer_wait": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P, C.c_int64, _P]),
     "fz_plan_begin": (C.c_int, [C.POINTER(_P)]),

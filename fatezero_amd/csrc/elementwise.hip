@@ -207,6 +207,23 @@ extern "C" int fz_accumulate(float* acc, const void* x, int64_t n, void* stream)
     return fz_last_launch_status();
 }
 
+// ---- y[r][i] = x[i], r < reps: the expanding copy at the end of a CFG-shared head where the consuming op has no broadcast form -------------
+FZ_KERNEL void __launch_bounds__(256) repeat_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, int64_t n8, int reps) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+        const half8_t v = fz_ld_h8(x + i * 8);
+        for (int r = 0; r < reps; ++r) fz_st_h8(y + ((int64_t)r * n8 + i) * 8, v);
+    }
+}
+
+extern "C" int fz_repeat(const void* x, void* y, int64_t n, int reps, void* stream) {
+    if (!x || !y || n <= 0 || (n & 7) || reps <= 0) return FZ_ERR_BAD_ARG;
+    const int64_t n8 = n >> 3;
+    int blocks = (int)((n8 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    FZ_LAUNCH(repeat_kernel, dim3(blocks), dim3(256), 0, stream, (const half_t*)x, (half_t*)y, n8, reps);
+    return fz_last_launch_status();
+}
+
 extern "C" const char* fz_version(void) {
 #ifdef FZ_EMU
     return "fatezero_amd 0.1 (CPU emulation build -- tests only)";

@@ -90,6 +90,7 @@ struct IgArgs {
     const half_t* res;   // [Nb][ldres] or null
     const half_t* res2;
     int64_t lda, ldb, ldy, ldres, a_bs, b_bs, y_bs, res_bs, temb_stride;
+    int64_t res_rows;    // > 0 (fz_gemm*, batch 1, Nb < 2^31): `res` holds res_rows rows, output row r adds res[r % res_rows]; res2 is per row
     int64_t Nb;          // B rows (tokens / output pixels) per batch element
     int64_t temb_group;
     int Ma, Ma_store;    // A rows; rows [Ma, Ma_store) of the output are written as zeros (V^T padding)
@@ -1091,6 +1092,7 @@ FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), 
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = co + e < Mo ? (float)v[e] : 0.0f;  // [Mo, Mo_store): zero padding
             const bool full = vec_ok && co + 8 <= Mo;
+            const int64_t pr = g.res_rows > 0 ? (int64_t)((uint32_t)px % (uint32_t)g.res_rows) : px;  // row of the (shared) residual
             if (full) {  // aligned 16-byte accesses
                 if (g.temb != nullptr) {
                     const half8_t t = fz_ld_h8(g.temb + (px / g.temb_group) * g.temb_stride + co);
@@ -1098,7 +1100,7 @@ FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), 
                     for (int e = 0; e < 8; ++e) f[e] += (float)t[e];
                 }
                 if (R1 != nullptr) {
-                    const half8_t r = fz_ld_h8(R1 + px * g.ldres + co);
+                    const half8_t r = fz_ld_h8(R1 + pr * g.ldres + co);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) f[e] += (float)r[e];
                 }
@@ -1114,7 +1116,7 @@ FZ_KERNEL void __launch_bounds__((IgCfg<WA, TA, WB, TB, BK, NS, GEGLU, PP>::T), 
                         if (co + e < Mo) f[e] += (float)t[e];
                 }
                 if (R1 != nullptr) {
-                    const half_t* r = R1 + px * g.ldres + co;
+                    const half_t* r = R1 + pr * g.ldres + co;
                     for (int e = 0; e < 8; ++e)
                         if (co + e < Mo) f[e] += (float)r[e];
                 }
@@ -1256,7 +1258,8 @@ FZ_KERNEL void __launch_bounds__(256) igemm_reduce_kernel(IgArgs g, int batch) {
         const float* const p0 = g.part + row * g.Ma;                      // slab 0: [batch][Nb][Ma]
         const int64_t slab = (int64_t)batch * g.Nb * g.Ma;
         const half_t* const trow = g.temb != nullptr ? g.temb + (px / g.temb_group) * g.temb_stride : nullptr;
-        const half_t* const r1 = g.res != nullptr ? g.res + (int64_t)z * g.res_bs + px * g.ldres : nullptr;
+        const int64_t pr = g.res_rows > 0 ? px % g.res_rows : px;  // (wave-uniform: one division per row)
+        const half_t* const r1 = g.res != nullptr ? g.res + (int64_t)z * g.res_bs + pr * g.ldres : nullptr;
         const half_t* const r2 = g.res2 != nullptr ? g.res2 + (int64_t)z * g.res_bs + px * g.ldres : nullptr;
         half_t* const yrow = g.y + (int64_t)z * g.y_bs + px * g.ldy;
         const int c4 = (int)blockIdx.y * 64 + cl;
@@ -1747,6 +1750,8 @@ extern "C" int fz_gemm(const FzGemmDesc* d, const void* x, const void* w, const 
     g.res2 = (const half_t*)res2;
     g.ldres = d->ldres ? d->ldres : d->ldy;
     g.res_bs = d->res_batch_stride;
+    if (d->res_rows < 0 || (d->res_rows > 0 && (batch != 1 || d->transpose_out || d->rows >= (1ll << 31)))) return FZ_ERR_BAD_ARG;
+    g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
     g.y = (half_t*)y;
     g.ldy = d->ldy;
     g.y_bs = d->y_batch_stride;
@@ -1925,6 +1930,8 @@ extern "C" int fz_gemm_gn(const FzGemmDesc* d, const void* x, const void* w, con
     g.y = (half_t*)y;
     g.ldy = d->ldy;
     g.ldres = d->ldres ? d->ldres : d->ldy;
+    if (d->res_rows < 0 || (d->res_rows > 0 && d->rows >= (1ll << 31))) return FZ_ERR_BAD_ARG;
+    g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
     const bool want = ig_gs_setup(g, gn_partial, gn_groups, rows_per_frame);
     const int rc = ig_run<0, false>(g, 1, d->tile_cfg, 1, nullptr, 0, stream);
     return rc != FZ_OK ? rc : (want ? FZ_OK : FZ_GEMM_NO_STATS);
@@ -1953,6 +1960,8 @@ extern "C" int fz_gemm_lnout(const FzGemmDesc* d, const void* x, const void* w, 
     g.y = (half_t*)y;
     g.ldy = d->ldy;
     g.ldres = d->ldres ? d->ldres : d->ldy;
+    if (d->res_rows < 0 || (d->res_rows > 0 && d->rows >= (1ll << 31))) return FZ_ERR_BAD_ARG;
+    g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
     g.lno_y = (half_t*)y_ln;
     g.lno_gamma = (const half_t*)gamma;
     g.lno_beta = (const half_t*)beta;

@@ -39,6 +39,7 @@ struct GnArgs {
     const half_t* x;
     const half_t* x2;  // channels [C1, C) come from a SECOND tensor [n][tokens][C - C1] (the skip connection of an up block:
     int C1;            // GroupNorm of torch.cat([x, skip], channel) without the concatenated copy); x2 == nullptr: C1 = C
+    int x2_frames;     // > 0: x2 holds x2_frames frames, frame n reads frame n % x2_frames of it (x2_frames % span == 0); 0: n_frames
     half_t* y;
     const half_t *gamma, *beta;
     float* partial;  // [n_frames][G][chunks][3]: the partials of one (frame, group) are contiguous
@@ -71,7 +72,8 @@ FZ_KERNEL void __launch_bounds__(ROWS > 0 ? 512 : 1024) gn_stats_kernel(GnArgs a
     // (a 16-byte chunk never straddles the two sources: C1 % 8 == 0)
     const bool second = v * 8 >= a.C1;
     const int64_t rs = second ? a.C - a.C1 : a.C1;  // row stride of this thread's source
-    const half_t* base = (second ? a.x2 + ((int64_t)n * a.tokens) * rs + (v * 8 - a.C1) : a.x + ((int64_t)n * a.tokens) * rs + v * 8);
+    const int n2 = a.x2_frames > 0 ? n % a.x2_frames : n;
+    const half_t* base = (second ? a.x2 + ((int64_t)n2 * a.tokens) * rs + (v * 8 - a.C1) : a.x + ((int64_t)n * a.tokens) * rs + v * 8);
     float s[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) s[e] = 0.0f;
@@ -262,7 +264,8 @@ FZ_KERNEL void gn_apply_kernel(GnArgs a) {
     }
     const bool second = v * 8 >= a.C1;
     const int64_t rs = second ? a.C - a.C1 : a.C1;
-    const half_t* xb = (second ? a.x2 + ((int64_t)n * a.tokens) * rs + (v * 8 - a.C1) : a.x + ((int64_t)n * a.tokens) * rs + v * 8);
+    const int n2 = a.x2_frames > 0 ? n % a.x2_frames : n;
+    const half_t* xb = (second ? a.x2 + ((int64_t)n2 * a.tokens) * rs + (v * 8 - a.C1) : a.x + ((int64_t)n * a.tokens) * rs + v * 8);
     half_t* yb = a.y + ((int64_t)n * a.tokens) * a.C + v * 8;
 #pragma unroll 4
     for (int t = t0 + r; t < t1; t += a.R) {
@@ -314,7 +317,9 @@ FZ_KERNEL void __launch_bounds__(GN_FUSED_THREADS) gn_fused_kernel(GnArgs a) {
     // two wave-uniform bases (x | the skip tensor of a lazy concatenation) + 32-bit element offsets; a group may straddle the seam
     const uint32_t rs1 = (uint32_t)a.C1, rs2 = (uint32_t)(a.C - a.C1);
     const half_t* const src1 = a.x + row0 * a.C1;
-    const half_t* const src2 = a.x2 != nullptr ? a.x2 + row0 * (a.C - a.C1) : src1;
+    // (a stat set never wraps around a broadcast x2: x2_frames % span == 0)
+    const int64_t row0_2 = a.x2_frames > 0 ? (int64_t)((sp * a.span) % a.x2_frames) * a.tokens : row0;
+    const half_t* const src2 = a.x2 != nullptr ? a.x2 + row0_2 * (a.C - a.C1) : src1;
     half_t* const dst = a.y + row0 * a.C + c0;
     // thread t owns pairs e = t + 1024 i: (row, pair) advance incrementally
     const int drow = GN_FUSED_THREADS / P, dpr = GN_FUSED_THREADS - drow * P;
@@ -408,7 +413,8 @@ FZ_KERNEL void __launch_bounds__(GN_FUSED_THREADS) gn_fused2_kernel(GnArgs a) {
     const int64_t row0 = (int64_t)sp * rows;
     const bool second = ch >= a.C1;
     const uint32_t rs = (uint32_t)(second ? a.C - a.C1 : a.C1);
-    const half_t* const src = second ? a.x2 + row0 * (a.C - a.C1) + (ch - a.C1) : a.x + row0 * a.C1 + ch;
+    const int64_t row0_2 = a.x2_frames > 0 ? (int64_t)((sp * a.span) % a.x2_frames) * a.tokens : row0;
+    const half_t* const src = second ? a.x2 + row0_2 * (a.C - a.C1) + (ch - a.C1) : a.x + row0 * a.C1 + ch;
     half_t* const dst = a.y + row0 * a.C + ch;
     const uint32_t step_in = (uint32_t)R * rs, step_out = (uint32_t)R * (uint32_t)a.C;
     const int r_first = active ? r0 : 0;
@@ -536,6 +542,7 @@ static int gn_setup(GnArgs& a, int n_frames, int span, int tokens, int channels,
     if (n_frames <= 0 || span <= 0 || n_frames % span || channels % 8 || channels % groups || groups > 64)
         return FZ_ERR_BAD_ARG;
     a.n_frames = n_frames; a.span = span; a.fin_span = span; a.tokens = tokens; a.C = channels; a.G = groups;
+    a.x2_frames = 0;
     a.tb = gn_tb(tokens, channels);
     a.chunks = fz_groupnorm_chunks(tokens, channels);
     a.pchunks = a.chunks;
@@ -573,15 +580,17 @@ extern "C" int fz_groupnorm(const void* x, void* y, const void* gamma, const voi
 
 extern "C" int fz_groupnorm_cat(const void* x1, int channels1, const void* x2, int channels2, void* y, const void* gamma,
                                 const void* beta, int n_frames, int span, int tokens, int groups, float eps, int silu, float* partial,
-                                void* stream) {
+                                int x2_frames, void* stream) {
     if (!x1 || !x2 || !y || !gamma || !beta || !partial || channels1 <= 0 || channels2 <= 0 || (channels1 % 8) || (channels2 % 8))
         return FZ_ERR_BAD_ARG;
+    if (x2_frames < 0 || (x2_frames > 0 && (span <= 0 || x2_frames % span || n_frames % x2_frames))) return FZ_ERR_BAD_ARG;
     GnArgs a;
     int threads;
     size_t smem;
     const int rc = gn_setup(a, n_frames, span, tokens, channels1 + channels2, groups, threads, smem);
     if (rc != FZ_OK) return rc;
     a.x = (const half_t*)x1; a.x2 = (const half_t*)x2; a.C1 = channels1;
+    a.x2_frames = x2_frames < n_frames ? x2_frames : 0;
     a.y = (half_t*)y; a.gamma = (const half_t*)gamma; a.beta = (const half_t*)beta;
     a.eps = eps; a.silu = silu;
     a.partial = partial;

@@ -122,6 +122,7 @@ struct XcArgs {
     half_t* y1;             // [rows][320]: attn1's result (hidden_states in front of attn2)
     int64_t rows, rows_per_frame;
     int frames_per_batch, lk;
+    int in_frames;          // > 0: xn / res hold in_frames frames and output frame n reads input frame n % in_frames (the CFG-shared head)
     float cs;               // softmax scale * log2(e)
     float eps, eps1;
 };
@@ -137,7 +138,10 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
     const int q8 = nt >> 3, r8 = nt & 7, xcd = bid & 7;
     const int blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int64_t row0 = (int64_t)blk * XC_ROWS + pair * 32;
-    const int batch = (int)(((int64_t)blk * XC_ROWS / g.rows_per_frame) / g.frames_per_batch);
+    const int64_t frame = (int64_t)blk * XC_ROWS / g.rows_per_frame;
+    const int batch = (int)(frame / g.frames_per_batch);
+    // the INPUT rows of this workgroup (a workgroup is 128 rows of one frame): the same rows of frame `frame % in_frames`; stores stay at row0
+    const int64_t in_shift = g.in_frames > 0 ? (frame % g.in_frames - frame) * g.rows_per_frame : 0;
     const char* const kv = g.kvpack + (int64_t)batch * (XC_H * XC_KVH * XC_FRAG);
     const char* const wmain = g.wpack + (FRONT ? XC_FRONTF * XC_FRAG : 0);
     unsigned char* const hbase = raw + XC_HOFF + pair * XC_HPAIR * XC_FRAG;
@@ -204,7 +208,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
         half8_t xb[XC_KS];  // the strip as B fragments: lane (row l31, k half hi) holds x[row][16 s + 8 hi .. + 8)
         const int64_t row = row0 + l31;
         {
-            const half_t* src = g.xn + row * XC_C + hi * 8;
+            const half_t* src = g.xn + (row + in_shift) * XC_C + hi * 8;
 #pragma unroll
             for (int s = 0; s < XC_KS; ++s) xb[s] = fz_ld_h8(src + s * 16);
         }
@@ -517,7 +521,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             // in the hand-over area as fragments (lane = row + 32 * k half, as the partner's accumulators want them).  Its loads are retired
             // by the vmcnt(0) in front of the barriers of ITS sub-steps (the odd ones) -- pinned there, in front of the next DMA issue.
             const int64_t row = row0 + l31;
-            const half_t* rs = g.res + row * XC_C + hi * 8;
+            const half_t* rs = g.res + (row + in_shift) * XC_C + hi * 8;
             half8_t ra[8];
 #pragma unroll
             for (int f = 0; f < 6; ++f) ra[f] = fz_ld_h8(rs + f * 16);            // pass 0: tiles 0..2 = fragments 0..5
@@ -626,7 +630,7 @@ FZ_KERNEL void __launch_bounds__(512, 2) xattn_chain_kernel(XcArgs g) {
             }
     }
     __syncthreads();
-    const half_t* resp = FRONT ? g.y1 : g.res;
+    const half_t* resp = FRONT ? g.y1 : (g.res != nullptr ? g.res + in_shift * XC_C : nullptr);
     const int l8 = lane & 7;
     FzRow5 gmv, btv;
     if (g.yln != nullptr) {
@@ -800,7 +804,7 @@ extern "C" int fz_xattn_chain_kv_pack(const void* k, int64_t k_batch_stride, int
 extern "C" int fz_xattn_chain(const FzXattnChain* d, void* stream) {
     if (!d || !d->x || !d->packed || !d->kv_packed || !d->y) return FZ_ERR_BAD_ARG;
     if (!fz_xattn_chain_ok(d->rows, d->rows_per_frame, d->channels, d->heads, d->lk)) return FZ_ERR_UNSUPPORTED;
-    if (d->frames_per_batch <= 0) return FZ_ERR_BAD_ARG;
+    if (d->frames_per_batch <= 0 || d->in_frames < 0) return FZ_ERR_BAD_ARG;
     if (d->y_ln != nullptr && (!d->ln_gamma || !d->ln_beta)) return FZ_ERR_BAD_ARG;
     const bool front = d->front != 0;
     if (front && (!d->res || !d->y1)) return FZ_ERR_BAD_ARG;
@@ -819,6 +823,7 @@ extern "C" int fz_xattn_chain(const FzXattnChain* d, void* stream) {
     g.rows_per_frame = d->rows_per_frame;
     g.frames_per_batch = d->frames_per_batch;
     g.lk = d->lk;
+    g.in_frames = d->in_frames > 0 && (int64_t)d->in_frames * d->rows_per_frame < d->rows ? d->in_frames : 0;
     g.cs = d->scale * 1.4426950408889634f;
     g.eps = d->ln_eps;
     g.eps1 = d->ln1_eps;

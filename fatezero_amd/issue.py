@@ -146,8 +146,9 @@ def recording():
 def _model_switches():
     """The module-level switches of the model code that change which kernels a forward launches (same-box A/B runs flip them at run time):
     a plan recorded under one setting is not the launch list of another."""
-    from .video_diffusion.models import attention as A, lora as Lo, resnet as R
-    return (A.QKV_FUSION, A.LN_FROM_PRODUCER, R.GN_FROM_EPILOGUE, Lo.LORA_PAIR_FUSION, Lo.LORA_PAIR_GN, Lo.LORA_PAIR_ALWAYS)
+    from .video_diffusion.models import attention as A, lora as Lo, resnet as R, unet_3d_condition as U
+    return (A.QKV_FUSION, A.LN_FROM_PRODUCER, A.FF_CHAIN, A.XATTN_CHAIN, A.XATTN_CHAIN_FRONT, R.GN_FROM_EPILOGUE, R.CONV_UP2,
+            Lo.LORA_PAIR_FUSION, Lo.LORA_PAIR_GN, Lo.LORA_PAIR_ALWAYS, U.CFG_SHARED_HEAD)
 
 
 class ForwardPlan:
@@ -309,7 +310,7 @@ class IssuePlans:
             sig = None if sig_fn is None or getattr(controller, "attention_plan", None) is None else sig_fn()
             if sig is None:
                 return None
-        return (tuple(x.data.shape), x.b, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
+        return (tuple(x.data.shape), x.b, x.rep, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
                 ctx.dtype, type(controller), sig, _model_switches())  # (sig carries the map format)
 
     # -- record --------------------------------------------------------------------------------------------

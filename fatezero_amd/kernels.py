@@ -327,10 +327,12 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, span:
 def groupnorm_cat(x1: torch.Tensor, x2: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, span: int, groups: int, eps: float,
                   silu: bool) -> torch.Tensor:
     """GroupNorm(+SiLU) of torch.cat([x1, x2], -1) without building the concatenation (fz_groupnorm_cat): x1 [N, tokens, C1],
-    x2 [N, tokens, C2] contiguous fp16 -> [N, tokens, C1 + C2]."""
+    x2 [N, tokens, C2] contiguous fp16 -> [N, tokens, C1 + C2].  x2 may hold FEWER frames, [N2, tokens, C2] with N % N2 == 0 and N2 % span == 0:
+    frame n of the concatenation then takes frame n % N2 of it (a skip tensor shared by the halves of the CFG batch)."""
     n, tokens, c1 = x1.shape
-    c2 = x2.shape[2]
-    if not (x1.is_contiguous() and x2.is_contiguous() and x2.shape[:2] == x1.shape[:2] and x1.dtype == x2.dtype == torch.float16
+    n2, c2 = x2.shape[0], x2.shape[2]
+    if not (x1.is_contiguous() and x2.is_contiguous() and x2.shape[1] == tokens and 0 < n2 <= n and n % n2 == 0 and n2 % span == 0
+            and x1.dtype == x2.dtype == torch.float16
             and gamma.dtype == beta.dtype == torch.float16 and gamma.numel() == c1 + c2):
         raise ValueError("fz_groupnorm_cat: two contiguous fp16 tensors [N, tokens, C1] / [N, tokens, C2], gamma / beta over C1 + C2")
     _chk16(x1, x2, gamma, beta)
@@ -346,7 +348,7 @@ def groupnorm_cat(x1: torch.Tensor, x2: torch.Tensor, gamma: torch.Tensor, beta:
         _scratch_gen[0] += 1
     out = torch.empty(n, tokens, c, dtype=torch.float16, device=x1.device)
     N.check(N.lib().fz_groupnorm_cat(x1.data_ptr(), c1, x2.data_ptr(), c2, out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n, span,
-                                     tokens, groups, eps, 1 if silu else 0, buf.data_ptr(), _stream(x1)), "fz_groupnorm_cat")
+                                     tokens, groups, eps, 1 if silu else 0, buf.data_ptr(), n2 if n2 < n else 0, _stream(x1)), "fz_groupnorm_cat")
     return out
 
 
@@ -397,7 +399,7 @@ def groupnorm_from_partial(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Ten
 
 
 def gemm_gn(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, res: Optional[torch.Tensor] = None, gn_groups: int,
-            rows_per_frame: int):
+            rows_per_frame: int, tile_cfg: int = 0):
     """y = x @ w^T + bias (+ res) as K.gemm, plus the GroupNorm(gn_groups) Welford partials of y [rows / rows_per_frame, gn_groups,
     rows_per_frame / 128, 3] out of the same launch (fz_gemm_gn); returns (y, partial or None)."""
     k, o = x.shape[-1], w.shape[0]
@@ -406,12 +408,13 @@ def gemm_gn(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, r
         return _gemm_unwrapped(x, w, bias, res=res), None
     _chk16(x, w, bias, res)
     y = torch.empty(tuple(x.shape[:-1]) + (o,), dtype=torch.float16, device=x.device)
-    if res is not None and (not res.is_contiguous() or res.shape != y.shape):
+    res_rows = _res_rows(res, rows, o)
+    if res is not None and (not res.is_contiguous() or (res.shape != y.shape and not res_rows)):
         return _gemm_unwrapped(x, w, bias, res=res), None
     d = N.FzGemmDesc()
     d.rows, d.in_features, d.out_features = rows, k, o
     d.ldx, d.ldw, d.ldy, d.ldres = k, w.stride(0), o, o
-    d.batch, d.epilogue = 1, N.FZ_GEMM_PLAIN
+    d.batch, d.epilogue, d.res_rows, d.tile_cfg = 1, N.FZ_GEMM_PLAIN, res_rows, tile_cfg
     partial = torch.empty(rows // rows_per_frame, gn_groups, rows_per_frame // 128, 3, dtype=torch.float32, device=x.device)
     rc = N.lib().fz_gemm_gn(C.byref(d), x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
                             None if res is None else res.data_ptr(), None, y.data_ptr(), partial.data_ptr(), gn_groups, rows_per_frame,
@@ -421,6 +424,19 @@ def gemm_gn(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, r
     if rc:
         N.check(rc, "fz_gemm_gn")
     return y, partial
+
+
+def _res_rows(res: Optional[torch.Tensor], rows: int, ow: int) -> int:
+    """FzGemmDesc.res_rows of a residual: 0 when it has one row per output row, its row count when it holds FEWER rows that divide the
+    output's (output row r adds res[r % res_rows]: a residual shared by the halves of the CFG batch)."""
+    if res is None:
+        return 0
+    rr = res.numel() // ow
+    if rr == rows:
+        return 0
+    if rr <= 0 or rows % rr or res.numel() != rr * ow:
+        raise ValueError(f"fz_gemm: a residual of {rr} rows cannot be broadcast over {rows} output rows")
+    return rr
 
 
 def pack_conv3x3_weight(w: torch.Tensor) -> torch.Tensor:
@@ -494,7 +510,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     The descriptor of a call signature (shapes / strides / flags) is validated and built once and then reused: per call only
     the pointers change."""
     key = (x.shape, x.stride(), w.shape, w.stride(0), geglu, tile_cfg, split_k, x.device,
-           None if res is None else res.stride(), res2 is not None, None if out is None else (out.shape, out.stride()))
+           None if res is None else (res.stride(), res.numel()), res2 is not None, None if out is None else (out.shape, out.stride()))
     plan = _gemm_plans.get(key)
     if plan is None:
         plan = _gemm_plans[key] = _gemm_plan(x, w, bias, res, res2, out, geglu, tile_cfg, split_k)
@@ -537,6 +553,7 @@ def gemm_lnout(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], l
     d.rows, d.in_features, d.out_features = rows, k, o
     d.ldx, d.ldw, d.ldy, d.ldres = k, w.stride(0), o, o
     d.batch, d.epilogue, d.tile_cfg, d.split_k = 1, N.FZ_GEMM_PLAIN, tile_cfg, split_k
+    d.res_rows = _res_rows(res, rows, o)
     want_ws = o % 4 == 0 and (k >= 1024 or split_k > 1) and 2 * rows * o <= _WS_FLOATS
     if want_ws:
         d.workspace_floats = _WS_FLOATS
@@ -599,9 +616,11 @@ def _gemm_plan(x, w, bias, res, res2, out, geglu, tile_cfg, split_k):
     d.ldx, d.ldw, d.ldy = ldx, w.stride(0), ldy
     d.batch, d.epilogue = 1, (N.FZ_GEMM_GEGLU if geglu else N.FZ_GEMM_PLAIN)
     d.tile_cfg, d.split_k = tile_cfg, split_k
+    d.res_rows = _res_rows(res, rows, ow)
     for r in (res, res2):
         if r is not None:
-            assert r.shape[-1] == ow and r.stride(-1) == 1 and r.numel() // ow == rows and r.dtype == torch.float16
+            assert r.shape[-1] == ow and r.stride(-1) == 1 and r.dtype == torch.float16
+            assert r.numel() // ow == rows or (r is res and d.res_rows and r.is_contiguous())
     if res is not None:
         d.ldres = res.stride(-2) if res.dim() > 1 else ow
         if res2 is not None:
@@ -756,12 +775,17 @@ def xattn_chain_kv_pack(k: torch.Tensor, vt: torch.Tensor, lk: int, out: Optiona
 
 
 def xattn_chain(x: torch.Tensor, packed: torch.Tensor, kv_packed: torch.Tensor, bias_out: Optional[torch.Tensor], *, res: Optional[torch.Tensor],
-                frames_per_batch: int, heads: int, lk: int, scale: float, ln=None, front_eps: Optional[float] = None):
-    """x: [N, L, 320] fp16 contiguous.  front_eps is None: x = LayerNorm'ed hidden states, returns (y, y_ln or None) with
+                frames_per_batch: int, heads: int, lk: int, scale: float, ln=None, front_eps: Optional[float] = None, out_frames: int = 0):
+    """out_frames > N (a multiple of it): x / res hold N frames and stand for out_frames -- output frame n reads input frame n % N (the CFG batch
+    fed ONE copy of the shared head's activations) and its context from n // frames_per_batch; every output has out_frames frames.
+    x: [N, L, 320] fp16 contiguous.  front_eps is None: x = LayerNorm'ed hidden states, returns (y, y_ln or None) with
     y = attn2(x, context) + res.  front_eps = eps of the LayerNorm in front (`packed` then holds attn1.to_out and that LayerNorm): x = attn1's
     attention output, `res` its residual; returns (y, y_ln or None, y1) with y1 = to_out1(x) + res and y = attn2(LayerNorm1(y1), context) + y1.
     (fz_xattn_chain)"""
-    n, l, c = x.shape
+    n_in, l, c = x.shape
+    n = out_frames or n_in
+    if n % n_in:
+        raise ValueError("fz_xattn_chain: out_frames must be a multiple of the input's frames")
     rows = n * l
     front = front_eps is not None
     ts = [x] + ([] if res is None else [res])
@@ -777,21 +801,22 @@ def xattn_chain(x: torch.Tensor, packed: torch.Tensor, kv_packed: torch.Tensor, 
         raise ValueError("fz_xattn_chain: `kv_packed` does not cover the batch")
     d = N.FzXattnChain()
     keep = [x, res, bias_out]
-    y = torch.empty_like(x)
+    y = torch.empty(n, l, c, dtype=x.dtype, device=x.device)
     yln = None
+    d.in_frames = n_in if n_in < n else 0
     d.x, d.res, d.packed, d.kv_packed, d.bias_out, d.y = x.data_ptr(), _ptr(res), packed.data_ptr(), kv_packed.data_ptr(), _ptr(bias_out), y.data_ptr()
     if ln is not None:
         gam, bet, eps = ln
         if gam.dtype != torch.float16 or bet.dtype != torch.float16:
             raise ValueError("fz_xattn_chain: LayerNorm weight / bias must be fp16")
-        yln = torch.empty_like(x)
+        yln = torch.empty_like(y)
         d.y_ln, d.ln_gamma, d.ln_beta, d.ln_eps = yln.data_ptr(), gam.data_ptr(), bet.data_ptr(), float(eps)
         keep += [gam, bet]
     y1 = None
     if front:
         if res is None:
             raise ValueError("fz_xattn_chain: the front form needs the residual")
-        y1 = torch.empty_like(x)
+        y1 = torch.empty_like(y)
         d.front, d.y1, d.ln1_eps = 1, y1.data_ptr(), float(front_eps)
     _chk16(*[t for t in keep if t is not None])
     d.rows, d.rows_per_frame, d.frames_per_batch, d.channels, d.heads, d.lk, d.scale = rows, l, frames_per_batch, c, heads, lk, float(scale)
@@ -1058,6 +1083,16 @@ def accumulate(acc: torch.Tensor, x: torch.Tensor):
     assert acc.is_contiguous() and x.is_contiguous()
     N.check(N.lib().fz_accumulate(_ptr(acc), _ptr(x), x.numel(), _stream(x)), "fz_accumulate")
     return acc
+
+
+def repeat_frames(x: torch.Tensor, reps: int) -> torch.Tensor:
+    """[N, ...] contiguous fp16 -> [reps * N, ...]: the data `reps` times in one launch (fz_repeat)."""
+    if x.dtype != torch.float16 or not x.is_contiguous() or x.numel() % 8 or reps < 1:
+        raise ValueError("fz_repeat: a contiguous fp16 tensor of a multiple of 8 elements")
+    _chk16(x)
+    out = torch.empty((reps * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    N.check(N.lib().fz_repeat(x.data_ptr(), out.data_ptr(), x.numel(), reps, _stream(x)), "fz_repeat")
+    return out
 
 
 def version() -> str:

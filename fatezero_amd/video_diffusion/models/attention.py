@@ -184,8 +184,9 @@ class CrossAttention(nn.Module):
     def forward_cross_after(self, x: Tokens, o1, attn1_out, hs, norm_in, ctx, clip: int, ln_next):
         """attn1's output projection + residual + `norm_in` AND this cross-attention + residual + `ln_next` in ONE launch (fz_xattn_chain, front
         form): o1 = attn1's attention output [N, L, C], hs = attn1's residual.  Falls back to the separate launches when the controller wants
-        the maps of this call.  Returns what forward_cross returns."""
+        the maps of this call.  Returns what forward_cross returns.  x.rep > 1: o1 / hs are shared by the halves of the batch, the results are not."""
         n, lq, c = o1.shape
+        n *= x.rep
         plan = _plan_for(self.controller, True, self.place_in_unet, n, clip, self.heads, lq, ctx.shape[1], o1.device)
         if plan is None or (plan.mode == K.FZ_ATTN_FLASH):
             _, _, kvp = self._context_kv(ctx, want_pack=True)
@@ -193,7 +194,7 @@ class CrossAttention(nn.Module):
             g3, b3 = ln_next.packed(o1.device)
             bo = self.to_out[0].packed(o1.dtype, o1.device)[1]
             y, yln, _ = K.xattn_chain(o1, packed, kvp, bo, res=hs, frames_per_batch=clip, heads=self.heads, lk=ctx.shape[1], scale=self.scale,
-                                      ln=(g3, b3, ln_next.eps), front_eps=norm_in.eps)
+                                      ln=(g3, b3, ln_next.eps), front_eps=norm_in.eps, out_frames=n)
             return y, yln
         hs1, n_in = _out_proj(attn1_out, o1, hs, norm_in)
         if n_in is None:
@@ -217,8 +218,12 @@ class CrossAttention(nn.Module):
     # -- cross attention (attention_register.py:71-128) ------------------------------------------------------
     def forward_cross(self, x: Tokens, ctx, clip: int, residual=None, ln_next=None, plan=False):
         """x.data: LayerNorm'ed hidden states [N, L, C]; ctx: [B, 77, Dctx] fp16.  Returns (residual + to_out(attention), LN of that by
-        `ln_next` or None): the block's `hidden_states = attn2(...) + hidden_states`, attention.py:303-311, fused into the GEMM epilogue."""
+        `ln_next` or None): the block's `hidden_states = attn2(...) + hidden_states`, attention.py:303-311, fused into the GEMM epilogue.
+        x.rep > 1 (the CFG-shared head ends HERE: the first op that reads the context): x.data and `residual` hold x.nb batch elements, the results
+        all x.b.  The chain launch reads the shared rows once per half (FzXattnChain.in_frames); the separate launches have no such form, so
+        the two shared tensors are expanded first, one copy launch each."""
         n, lq, c = x.data.shape
+        n *= x.rep  # (the controller and the launch-form choice see the frames of the whole batch, as without the shared head)
         ctrl = self.controller
         if plan is False:  # (a plan handed in was already taken from the controller for THIS call: forward_cross_after's fall-back)
             if (ln_next is not None and residual is not None and residual.is_contiguous()
@@ -230,7 +235,10 @@ class CrossAttention(nn.Module):
                     g3, b3 = ln_next.packed(xn.device)
                     return K.xattn_chain(xn, self._chain_weights(xn.device), kvp, self.to_out[0].packed(xn.dtype, xn.device)[1],
                                          res=residual, frames_per_batch=clip, heads=self.heads, lk=ctx.shape[1], scale=self.scale,
-                                         ln=(g3, b3, ln_next.eps))
+                                         ln=(g3, b3, ln_next.eps), out_frames=n)
+        if x.rep > 1:
+            residual = None if residual is None else K.repeat_frames(residual.contiguous(), x.rep)
+            x = x.expanded()
         q = self.to_q.apply(x.data)
         kk, vt, _ = self._context_kv(ctx)
         lk = ctx.shape[1]
@@ -336,7 +344,22 @@ class _ShardedKV:
 class SparseCausalAttention(CrossAttention):
     """attention.py:340-422 / attention_register.py:131-218: frame f attends the K/V of frames idx_j(f)."""
 
-    def forward_self(self, x: Tokens, clip: int, index_list, residual=None, ln_next=None, raw_out=False):
+    def self_plan(self, x: Tokens, clip: int, index_list):
+        """The controller's plan for this layer's call on `x` (all x.b batch elements, whether or not x.data holds every one): taken ONCE per
+        call -- the controller counts them -- and handed to forward_self."""
+        n, lq, _ = x.data.shape
+        return _plan_for(self.controller, False, self.place_in_unet, n * x.rep, clip, self.heads, lq, max(1, len(index_list)) * lq, x.data.device)
+
+    @staticmethod
+    def plan_is_plain(plan, lq):
+        """One plain FLASH launch over all frames, nothing captured or injected: the call computes the same thing for equal inputs, so a
+        CFG-shared input can stay shared through it.  Decided from the plan alone."""
+        if plan is None:  # a foreign controller: bypassed above 32 x 32 queries, otherwise it sees (and may edit) every frame's map
+            return lq > 32 ** 2
+        return plan.mode == K.FZ_ATTN_FLASH and plan.capture_first is None
+
+    def forward_self(self, x: Tokens, clip: int, index_list, residual=None, ln_next=None, raw_out=False, plan=False):
+        """plan: the controller's plan for this call where the caller already took it (self_plan); x.rep > 1 only with a plain plan."""
         n, lq, c = x.data.shape
         xn = x.data
         # head dims with a free MFMA contraction slot (SD-1.x: 40): the softmax scale and log2(e) go into Wq, q comes out of
@@ -373,7 +396,10 @@ class SparseCausalAttention(CrossAttention):
         out = torch.empty(n, lq, self.inner_dim, dtype=xn.dtype, device=xn.device)
         n_kv = max(1, len(index_list))
         ctrl = self.controller
-        plan = _plan_for(ctrl, False, self.place_in_unet, n, clip, self.heads, lq, n_kv * lq, xn.device)
+        if plan is False:
+            plan = _plan_for(ctrl, False, self.place_in_unet, n * x.rep, clip, self.heads, lq, n_kv * lq, xn.device)
+        if x.rep > 1 and not self.plan_is_plain(plan, lq):
+            raise RuntimeError("forward_self: a CFG-shared input needs a plain attention plan (expand it first)")
         if plan is None:
             if lq > 32 ** 2:
                 K.attn_self(q, kk, vt, out, mode=K.FZ_ATTN_FLASH, **kw)
@@ -485,22 +511,33 @@ class SpatioTemporalTransformerBlock(nn.Module):
         return self.model_config.get("SparseCausalAttention_index", [-1, "first"])  # attention.py:347 default
 
     def forward_tokens(self, x: Tokens, ctx, prenorm1=None):
+        """x.rep > 1 (the CFG-shared head): x.data / prenorm1 hold x.nb batch elements.  The shared part ends at attn2 -- the first op that reads
+        the text context -- or in front of attn1 when the controller's plan for that self-attention is anything but one plain FLASH launch
+        (a level of at most 32 x 32 queries whose cond half is captured or injected).  The result holds every batch element."""
         hs = x.data
         clip = x.f
         lnp = LN_FROM_PRODUCER and hs.shape[-1] == LN_FROM_PRODUCER_C and hs.dtype == torch.float16 and D.active_shard() is None
         # every `x = f(norm(x)) + x` of attention.py:295-337 ends in a GEMM: the residual add is that GEMM's epilogue -- and at the 320-channel
         # level so is the LayerNorm that opens the next step (`lnp`; None where the launch cannot produce it and the LayerNorm kernel runs)
         n1 = prenorm1 if prenorm1 is not None else layer_norm_tokens(self.norm1, hs)
+        plan1 = False
+        if x.rep > 1:
+            plan1 = self.attn1.self_plan(x, clip, self.sc_index)
+            if not self.attn1.plan_is_plain(plan1, hs.shape[1]):  # the halves differ from here on: the two shared tensors, one copy launch each
+                hs, n1 = K.repeat_frames(hs.contiguous(), x.rep), K.repeat_frames(n1.contiguous(), x.rep)
+                x = Tokens(hs, x.b, x.f, x.h, x.w)
+        n_all = hs.shape[0] * x.rep
         if (lnp and XATTN_CHAIN_FRONT and hs.is_contiguous()
-                and self.attn2._chain_applies(hs.shape[0], hs.shape[1], hs.shape[2], hs.dtype, ctx)):
+                and self.attn2._chain_applies(n_all, hs.shape[1], hs.shape[2], hs.dtype, ctx)):
             # attn1.to_out + residual + norm2 -> attn2 (to_q, cross-attention, to_out) + residual + norm3: ONE launch behind the self-attention
-            o1 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, raw_out=True)
+            o1 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, raw_out=True, plan=plan1)
             hs, n3 = self.attn2.forward_cross_after(x, o1, self.attn1.to_out[0], hs, self.norm2, ctx, clip, self.norm3)
         else:
-            hs, n2 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, residual=hs, ln_next=self.norm2 if lnp else None)
+            hs, n2 = self.attn1.forward_self(x.like(n1), clip, self.sc_index, residual=hs, ln_next=self.norm2 if lnp else None, plan=plan1)
             if n2 is None:
                 n2 = layer_norm_tokens(self.norm2, hs)
             hs, n3 = self.attn2.forward_cross(x.like(n2), ctx, clip, residual=hs, ln_next=self.norm3 if lnp else None)
+        x = Tokens(hs, x.b, x.f, x.h, x.w)  # (every batch element from attn2 on)
         if n3 is None:
             n3 = layer_norm_tokens(self.norm3, hs)
         hs, nt = self.ff.apply(n3, res=hs, ln_next=self.norm_temporal if lnp else None)
@@ -532,6 +569,8 @@ class SpatioTemporalTransformerModel(nn.Module):
         self.proj_out = _Conv1x1Params(inner, in_channels, linear=use_linear_projection)
 
     def forward_tokens(self, x: Tokens, ctx) -> Tokens:
+        """x.rep > 1 (the CFG-shared head): GroupNorm, proj_in (+ norm1) and the block up to its divergence point run on the shared data; proj_out
+        adds the shared x as a broadcast residual (FzGemmDesc.res_rows) and the result holds every batch element."""
         h = group_norm_tokens(self.norm, x, span_frames=False, silu=False)
         blk = self.transformer_blocks[0]
         pre1 = None
@@ -547,10 +586,10 @@ class SpatioTemporalTransformerModel(nn.Module):
             # the next consumer is a GroupNorm (the following resnet's norm1 / conv_norm_out) with the UNet's group count: where the
             # projection runs on a 320-wide tile its epilogue writes that norm's statistics partials (fz_gemm_gn)
             y, part = self.proj_out.apply_gn(h.data, res=x.data, groups=self.norm.num_groups, rows_per_frame=x.data.shape[1])
-            out = x.like(y)
+            out = h.like(y)
             out.gn = None if part is None else (part, self.norm.num_groups)
             return out
-        return x.like(self.proj_out.apply(h.data, res=x.data))
+        return h.like(self.proj_out.apply(h.data, res=x.data))
 
 
 class _Conv1x1Params(nn.Module):

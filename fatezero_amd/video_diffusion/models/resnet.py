@@ -28,18 +28,37 @@ CONV_UP2 = os.environ.get("FZ_NO_CONV_UP2") is None
 class Tokens:
     """A token-major activation: data [N, H*W, C] fp16 plus its frame geometry.  `gn` (optional): (partial, groups) -- the Welford partials
     of this tensor's GroupNorm statistics, written by the epilogue of the launch that produced it (fz_temporal_conv3_gn / fz_gemm_gn): the
-    GroupNorm that consumes the tensor then skips its statistics pass.  Never inherited by `like()`: it describes exactly this data."""
-    __slots__ = ("data", "b", "f", "h", "w", "gn")
+    GroupNorm that consumes the tensor then skips its statistics pass.  Never inherited by `like()`: it describes exactly this data.
+    `rep` (shared batch factor, default 1): the tensor holds b / rep batch elements of data and STANDS FOR b -- the same data `rep` times.  The
+    CFG edit feeds the UNet the same latents for both halves of its batch; until the text context enters, every activation is the same in both
+    (unet_3d_condition.py: CFG_SHARED_HEAD).  Ops of that head run on the b / rep elements and hand `rep` on (`like()`); the op where the halves
+    diverge reads the shared rows once per half (FzXattnChain.in_frames, FzGemmDesc.res_rows, fz_groupnorm_cat's x2_frames), anything else gets
+    `expanded()`."""
+    __slots__ = ("data", "b", "f", "h", "w", "gn", "rep")
 
-    def __init__(self, data, b, f, h, w, gn=None):
-        self.data, self.b, self.f, self.h, self.w, self.gn = data, b, f, h, w, gn
+    def __init__(self, data, b, f, h, w, gn=None, rep=1):
+        self.data, self.b, self.f, self.h, self.w, self.gn, self.rep = data, b, f, h, w, gn, rep
+        if b % rep:
+            raise ValueError(f"Tokens: a batch of {b} cannot be {rep} copies of anything")
 
     @property
     def c(self):
         return self.data.shape[-1]
 
+    @property
+    def nb(self):
+        """Batch elements the data really holds."""
+        return self.b // self.rep
+
     def like(self, data, h=None, w=None):
-        return Tokens(data, self.b, self.f, self.h if h is None else h, self.w if w is None else w)
+        return Tokens(data, self.b, self.f, self.h if h is None else h, self.w if w is None else w, rep=self.rep)
+
+    def expanded(self):
+        """The same activation with every batch element present (rep = 1): one copy launch (fz_repeat) where rep > 1."""
+        if self.rep == 1:
+            return self
+        d = self.data if self.data.is_contiguous() else self.data.contiguous()
+        return Tokens(K.repeat_frames(d, self.rep), self.b, self.f, self.h, self.w)
 
     @staticmethod
     def cat(a, b):
@@ -62,13 +81,20 @@ class CatTokens(Tokens):
     __slots__ = ("parts", "_cat")
 
     def __init__(self, a: Tokens, b: Tokens):
+        # (a skip of the CFG-shared head -- conv_in's output -- may hold FEWER frames than the tensor it is concatenated to: parts[1] is then
+        #  read once per half, group_norm_tokens / PseudoConv3d's 1x1 shortcut; the concatenation itself is not shared)
+        if a.rep != 1:
+            a = a.expanded()
         self.parts, self._cat = (a.data, b.data), None
-        self.b, self.f, self.h, self.w, self.gn = a.b, a.f, a.h, a.w, None
+        self.b, self.f, self.h, self.w, self.gn, self.rep = a.b, a.f, a.h, a.w, None, 1
 
     @property
     def data(self):
         if self._cat is None:
-            self._cat = torch.cat(self.parts, dim=-1)  # channel concat == last-dim concat in token-major
+            p0, p1 = self.parts
+            if p1.shape[0] != p0.shape[0]:
+                p1 = K.repeat_frames(p1.contiguous(), p0.shape[0] // p1.shape[0])
+            self._cat = torch.cat((p0, p1), dim=-1)  # channel concat == last-dim concat in token-major
         return self._cat
 
     @property
@@ -129,6 +155,8 @@ class PseudoConv3d(nn.Module):
 
     def forward_tokens(self, x: Tokens, residual=None, temb=None, upsample=False, gn_groups: int = 0) -> Tokens:
         """conv (+ temporal conv) (+ temb[b] per batch element) (+ residual). temb: [B, Cout] view, residual: [N, T, Cout].
+        x.rep > 1 (the CFG-shared head): everything runs on the x.nb batch elements the data holds -- `residual` too -- with the time-embedding
+        rows of the first x.nb batch elements (one timestep for the whole batch), and the result carries `rep` on.
         gn_groups > 0: the caller will GroupNorm the result with that many groups -- where the layer's LAST launch can emit the statistics
         from its epilogue (the LoRA up convolution on a 320-wide tile) the result carries them (`Tokens.gn`).
         Every spatial convolution of the UNet -- all pyramid levels, conv_in, conv_out, the 1x1 shortcuts -- runs through
@@ -137,6 +165,9 @@ class PseudoConv3d(nn.Module):
         probe = x.parts[0] if isinstance(x, CatTokens) and x._cat is None else x.data  # (do not materialise a lazy concatenation)
         w, bias, wtt, btt = self._pack(probe.dtype, probe.device)
         n, hw = probe.shape[0], probe.shape[1]
+        nb = x.nb
+        if temb is not None and temb.shape[0] != nb:
+            temb = temb[:nb]
         lora = self.conv_temporal if isinstance(self.conv_temporal, LoRALinearLayer) else None
         plain_t = self.conv_temporal is not None and lora is None and wtt is not None
         temporal_active = plain_t or (lora is not None and not lora.is_noop(probe.dtype, probe.device))
@@ -146,7 +177,12 @@ class PseudoConv3d(nn.Module):
             # 1x1 convolution of a lazy channel concatenation: W = [W1 | W2] along K, y = x1 W1^T + bias, then += x2 W2^T
             # (the second GEMM takes the first one's output as its residual)
             c1 = x.parts[0].shape[-1]
-            y = K.gemm(x.parts[1], w[:, c1:], None, res=K.gemm(x.parts[0], w[:, :c1], bias))
+            if x.parts[1].shape[0] != x.parts[0].shape[0]:
+                # the skip is shared by the halves of the CFG batch: its product once, on the frames it holds, then broadcast as the
+                # residual of the other half's GEMM (FzGemmDesc.res_rows) -- no expanding copy, and half the multiply-adds of this half
+                y = K.gemm(x.parts[0], w[:, :c1], bias, res=K.gemm(x.parts[1], w[:, c1:], None))
+            else:
+                y = K.gemm(x.parts[1], w[:, c1:], None, res=K.gemm(x.parts[0], w[:, :c1], bias))
             oh, ow = x.h, x.w
             fused = fuse_tail
         elif self.kernel_size == 1:
@@ -171,16 +207,16 @@ class PseudoConv3d(nn.Module):
                 fused = fuse_tail
         gn = None
         if lora is not None and temporal_active:
-            y4 = lora.forward_tokens(y.view(x.b, x.f, oh * ow, self.out_channels), temb=temb, residual=residual, gn_groups=gn_groups)
+            y4 = lora.forward_tokens(y.view(nb, x.f, oh * ow, self.out_channels), temb=temb, residual=residual, gn_groups=gn_groups)
             if isinstance(y4, tuple):
                 y4, part = y4
                 gn = None if part is None else (part, gn_groups)
             y = y4.reshape(n, oh * ow, self.out_channels)
             fused = True
         elif plain_t:
-            rows = btt[None, :].expand(x.b, -1) if temb is None else temb + btt
+            rows = btt[None, :].expand(nb, -1) if temb is None else temb + btt
             shard = D.active_shard()
-            y4 = y.view(x.b, x.f, oh * ow, self.out_channels)
+            y4 = y.view(nb, x.f, oh * ow, self.out_channels)
             if shard is not None:  # frames split over ranks: one-frame halo from both neighbours, halo outputs dropped
                 y4 = temporal_conv_tokens(shard.with_halo(y4, 1, 1, zero_outside=True, tag="temporal_conv"), wtt, rows_add=rows.contiguous())[:, 1:-1]
                 y = y4.reshape(n, oh * ow, self.out_channels)
@@ -191,7 +227,7 @@ class PseudoConv3d(nn.Module):
             fused = True
         if not fused:
             if temb is not None:
-                y = (y.view(x.b, x.f * oh * ow, self.out_channels) + temb[:, None, :]).view(n, oh * ow, self.out_channels)
+                y = (y.view(nb, x.f * oh * ow, self.out_channels) + temb[:, None, :]).view(n, oh * ow, self.out_channels)
             if residual is not None:
                 y = y + residual
         out = x.like(y, oh, ow)
@@ -231,13 +267,14 @@ def group_norm_tokens(norm: _NormParams, x: Tokens, *, span_frames: bool, silu: 
     if not lazy and x.gn is not None and x.gn[1] == norm.num_groups and x.gn[0].shape[0] == x.data.shape[0]:
         # the producer's epilogue already wrote the statistics partials: merge + normalise only
         y = K.groupnorm_from_partial(x.data, g, b, x.gn[0], span=(x.f if span_frames else 1), groups=norm.num_groups, eps=norm.eps, silu=silu)
-        return Tokens(y, x.b, x.f, x.h, x.w)
+        return x.like(y)
     if isinstance(x, CatTokens) and x._cat is None and x.parts[0].shape[-1] % 8 == 0 and x.parts[1].shape[-1] % 8 == 0:
+        # (parts[1] with fewer frames -- a skip shared by the halves of the CFG batch -- is read once per half: fz_groupnorm_cat's x2_frames)
         y = K.groupnorm_cat(x.parts[0], x.parts[1], g, b, span=(x.f if span_frames else 1), groups=norm.num_groups, eps=norm.eps,
                             silu=silu)
         return Tokens(y, x.b, x.f, x.h, x.w)
     y = K.groupnorm(x.data, g, b, span=(x.f if span_frames else 1), groups=norm.num_groups, eps=norm.eps, silu=silu)
-    return Tokens(y, x.b, x.f, x.h, x.w)
+    return x.like(y)
 
 
 def upsample_nearest2x(x: Tokens) -> Tokens:

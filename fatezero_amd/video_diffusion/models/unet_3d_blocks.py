@@ -37,6 +37,8 @@ class CrossAttnDownBlockPseudo3D(nn.Module):
                                                                   padding=1, name="op", model_config=model_config)])
 
     def forward_tokens(self, x: Tokens, temb_act, ctx):
+        """x.rep > 1 (the CFG-shared head): the first resnet and the first transformer up to the op that reads the text context run once for
+        all halves of the batch; the transformer returns every batch element (attention.py)."""
         outs = []
         for resnet, attn in zip(self.resnets, self.attentions):
             x = attn.forward_tokens(resnet.forward_tokens(x, temb_act), ctx)
@@ -63,6 +65,7 @@ class DownBlockPseudo3D(nn.Module):
 
     def forward_tokens(self, x: Tokens, temb_act, ctx=None):
         outs = []
+        x = x.expanded()  # (a CFG-shared input ends here: only a cross-attention down block carries the shared head further)
         for resnet in self.resnets:
             x = resnet.forward_tokens(x, temb_act)
             outs.append(x)
@@ -85,7 +88,7 @@ class UNetMidBlockPseudo3DCrossAttn(nn.Module):
                                                       resnet_groups, model_config, use_linear_projection)])
 
     def forward_tokens(self, x: Tokens, temb_act, ctx):
-        x = self.resnets[0].forward_tokens(x, temb_act)
+        x = self.resnets[0].forward_tokens(x.expanded(), temb_act)
         x = self.attentions[0].forward_tokens(x, ctx)
         return self.resnets[1].forward_tokens(x, temb_act)
 
@@ -116,6 +119,7 @@ class CrossAttnUpBlockPseudo3D(nn.Module):
                                                               model_config=model_config)])
 
     def forward_tokens(self, x: Tokens, skips, temb_act, ctx):
+        x = x.expanded()
         for resnet, attn in zip(self.resnets, self.attentions):
             x = resnet.forward_tokens(_cat_skip(x, skips.pop()), temb_act)
             x = attn.forward_tokens(x, ctx)
@@ -143,6 +147,7 @@ class UpBlockPseudo3D(nn.Module):
                                                               model_config=model_config)])
 
     def forward_tokens(self, x: Tokens, skips, temb_act, ctx=None):
+        x = x.expanded()
         for resnet in self.resnets:
             x = resnet.forward_tokens(_cat_skip(x, skips.pop()), temb_act)
         if self.upsamplers is not None:

@@ -68,6 +68,19 @@ def _check_newer_keys(kwargs, attention_head_dim):
 
 
 TIME_EMBED_CACHE = True  # (switch for same-box A/B runs: False = the timestep enters as a device tensor at every forward, as before)
+# The CFG-shared head (round 7).  Every step of the classifier-free-guidance edit feeds the UNet the SAME latents for both halves of its batch; the
+# halves differ only through the text context, which first enters at attn2 of the first transformer block.  With the switch on, the edit loop hands
+# the UNet ONE copy of the latents marked `Tokens.rep = 2` and everything in front of that op -- conv_in, the first resnet, GroupNorm / proj_in /
+# norm1 / attn1 (+ to_out, norm2) of the first transformer -- runs once instead of twice; the ops at the divergence point read the shared rows once
+# per half (FzXattnChain.in_frames, FzGemmDesc.res_rows, fz_groupnorm_cat's x2_frames).  Only a caller that KNOWS its halves are equal passes
+# rep > 1 (the pipeline's _LatentState); `UNet.forward` and rep = 1 callers are never deduplicated.  Off (the input is expanded on entry) with the
+# switch False -- same-box A/B runs: scripts/ab_bench.py <this module> CFG_SHARED_HEAD -- and under a frame shard.
+CFG_SHARED_HEAD = True
+
+
+def cfg_shared_head_active():
+    from ... import dist as D
+    return CFG_SHARED_HEAD and D.active_shard() is None
 
 
 class UNetPseudo3DConditionModel(nn.Module):
@@ -234,6 +247,8 @@ class UNetPseudo3DConditionModel(nn.Module):
         """x: latents as tokens [B*F, H*W, 4] fp16; ctx [B, 77, D] fp16 -> predicted noise, same layout."""
         from ... import kernels as K
         K.refresh_stream()
+        if x.rep > 1 and not cfg_shared_head_active():
+            x = x.expanded()
         temb_act = self.time_embed(timestep, x.b, x.data.device)
         ctx = ctx.to(torch.float16)
         issuer = self._issuer

@@ -20,30 +20,34 @@ import torch
 from ... import dist as fz_dist
 from ... import kernels as K
 from ..models.resnet import Tokens
+from ..models.unet_3d_condition import cfg_shared_head_active
 from ..prompt_attention import attention_util, spatial_blend
 from .stable_diffusion import SpatioTemporalStableDiffusionPipeline, StableDiffusionPipelineOutput
 
 
 class _LatentState:
-    """fp32 master latents [4, F, hw] + the fp16 token-major UNet input [reps*F, hw, 4]."""
+    """fp32 master latents [4, F, hw] + the fp16 token-major UNet input.  The `reps` halves of the CFG batch are the SAME latents: with the
+    UNet's CFG-shared head (unet_3d_condition.py: CFG_SHARED_HEAD; never under a frame shard) the input is ONE copy [F, hw, 4] handed out as
+    `Tokens(..., b=reps, rep=reps)`; otherwise [reps*F, hw, 4] with the copies written out."""
 
-    def __init__(self, latents: torch.Tensor, reps: int):
+    def __init__(self, latents: torch.Tensor, reps: int, share: bool = True):
         b, c, f, h, w = latents.shape
         if b != 1:
             raise ValueError("Only support single video editing")  # attention_util.py:192 of the reference
         self.f, self.h, self.w, self.reps = f, h, w, reps
+        self.copies = 1 if (reps > 1 and share and cfg_shared_head_active()) else reps  # copies of the latents the token buffer holds
         # always a private copy: the master buffer is updated in place every step and must never alias the caller's latents
         self.z = latents[0].to(torch.float32, copy=True).reshape(c, f, h * w).contiguous()
-        self.tok = torch.empty(reps * f, h * w, c, dtype=torch.float16, device=latents.device)
+        self.tok = torch.empty(self.copies * f, h * w, c, dtype=torch.float16, device=latents.device)
         self.sync_tokens()
 
     def sync_tokens(self):
         t = self.z.permute(1, 2, 0).to(torch.float16)
-        for r in range(self.reps):
+        for r in range(self.copies):
             self.tok[r * self.f:(r + 1) * self.f].copy_(t)
 
     def tokens(self) -> Tokens:
-        return Tokens(self.tok, self.reps, self.f, self.h, self.w)
+        return Tokens(self.tok, self.reps, self.f, self.h, self.w, rep=self.reps // self.copies)
 
     def as_latents(self, dtype) -> torch.Tensor:
         return self.z.view(1, self.z.shape[0], self.f, self.h, self.w).to(dtype)
@@ -54,7 +58,7 @@ class _LatentState:
 
     def update(self, eps_u, eps_c, guidance, cz, ce):
         K.latent_update(self.z, eps_u, eps_c, guidance, cz, ce, next_in=self.tok[: self.f])
-        for r in range(1, self.reps):
+        for r in range(1, self.copies):
             self.tok[r * self.f:(r + 1) * self.f].copy_(self.tok[: self.f])
 
 
@@ -270,7 +274,7 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         shard = self.frame_shard
         if shard is not None:
             latents = shard.local(latents, 2).contiguous()
-        state = _LatentState(latents.detach(), reps=2 if do_cfg else 1)
+        state = _LatentState(latents.detach(), reps=2 if do_cfg else 1, share=shard is None)
         emb = text_embeddings.to(torch.float16)
         n_t = len(timesteps)
         with fz_dist.frame_sharded(shard):

@@ -155,9 +155,11 @@ int fz_groupnorm(const void* x, void* y, const void* gamma, const void* beta, in
 /* The same on torch.cat([x1, x2], channel) WITHOUT the concatenated copy: the skip connections of the up blocks
  * (unet_3d_blocks.py:384-395 `hidden_states = torch.cat([hidden_states, res_hidden_states], dim=1)` feeding
  * ResnetBlockPseudo3D.norm1, resnet.py:338).  x1: [n][tokens][channels1], x2: [n][tokens][channels2], y: [n][tokens][channels1 +
- * channels2] = the normalised concatenation; gamma / beta over channels1 + channels2; channels1, channels2 % 8 == 0. */
+ * channels2] = the normalised concatenation; gamma / beta over channels1 + channels2; channels1, channels2 % 8 == 0.
+ * x2_frames > 0: x2 holds x2_frames frames and frame n of the concatenation takes frame n % x2_frames of it (a skip tensor shared by the
+ * halves of the CFG batch; x2_frames % span == 0 and n_frames % x2_frames == 0); 0: x2 holds n_frames frames. */
 int fz_groupnorm_cat(const void* x1, int channels1, const void* x2, int channels2, void* y, const void* gamma, const void* beta,
-                     int n_frames, int span, int tokens, int groups, float eps, int silu, float* partial, void* stream);
+                     int n_frames, int span, int tokens, int groups, float eps, int silu, float* partial, int x2_frames, void* stream);
 
 /* The two halves of fz_groupnorm for statistics that span frames living on several GPUs:
  *   fz_groupnorm_stats  writes this rank's Welford partials  partial[n_frames][G][chunks][3] = (count, mean, M2);
@@ -204,6 +206,8 @@ typedef struct FzGemmDesc {
     int64_t w_batch_stride; /* elements between the w matrices of consecutive batch elements; 0: w (and bias) shared by the batch.
                              * Per-batch w = the two batched products of a single-head attention block: scores = q k^T and P v^T^T
                              * (diffusers AttentionBlock of the VAE mid block [3P], reached from stable_diffusion.py:297-319). */
+    int64_t res_rows;       /* > 0: `res` holds res_rows rows and output row r adds res[r % res_rows] (a residual shared by the halves of
+                             * the CFG batch; res2 is not broadcast); batch == 1, rows < 2^31.  0: one residual row per output row.  */
 } FzGemmDesc;
 int64_t fz_gemm_workspace_floats(int64_t rows, int out_features, int batch);
 int fz_gemm(const FzGemmDesc* desc, const void* x, const void* w, const void* bias, const void* res, const void* res2,
@@ -265,6 +269,9 @@ typedef struct FzXattnChain {
     float scale;            /* softmax scale (head_dim ** -0.5)                                                           */
     float ln_eps, ln1_eps;
     int32_t front;
+    int32_t in_frames;      /* > 0: x and res hold in_frames frames; output frame n reads the rows of input frame n % in_frames
+                             * (the CFG batch fed ONE copy of the shared head's activations); 0: one input frame per output frame  */
+    int32_t reserved0;
 } FzXattnChain;
 int fz_xattn_chain_ok(int64_t rows, int64_t rows_per_frame, int channels, int heads, int lk);
 int fz_xattn_chain_preferred(int64_t rows, int64_t rows_per_frame, int channels, int heads, int lk);
@@ -403,6 +410,11 @@ int fz_latent_update(float* z, const void* eps_u, const void* eps_c, float guida
 /* fp16 running-sum helper for the edit controller's accumulated cross maps (attention_store.py:95-101):
  * acc (float) += x (fp16), n elements. */
 int fz_accumulate(float* acc, const void* x, int64_t n, void* stream);
+
+/* y[r][i] = x[i] for r < reps (fp16, n % 8 == 0, 16-byte aligned): the one expanding copy at the end of a CFG-shared head where the op that
+ * consumes the shared tensor has no broadcast form (FzXattnChain.in_frames, FzGemmDesc.res_rows and fz_groupnorm_cat's x2_frames are the
+ * broadcast forms). */
+int fz_repeat(const void* x, void* y, int64_t n, int reps, void* stream);
 
 /* One-sided exchanges between the GPUs that share ONE frame-sharded clip (csrc/peer.hip): every rank owns a symmetric
  * heap its peers have mapped (hipIpc over xGMI).  The couplings they carry: 5-D GroupNorm statistics (resnet.py:338,369), the halo
