@@ -108,6 +108,8 @@ _SIGS = {
                                       C.c_int64, C.c_int64, C.c_float, _P]),
     "fz_blend_mask": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, _P,
                                 C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "fz_blend_mask_hw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P,
+                                   C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "fz_groupnorm_chunks": (C.c_int, [C.c_int, C.c_int]),
     "fz_groupnorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                _P, _P]),

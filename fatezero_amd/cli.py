@@ -115,6 +115,11 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
 
     prompt_ids = tokenizer(dataset_config["prompt"], truncation=True, padding="max_length", max_length=tokenizer.model_max_length,
                            return_tensors="pt").input_ids
+    # a [height, width] image_size is checked here, against what the VAE and the UNet's downsamplers divide a side by, not inside the UNet
+    dataset_config = dict(dataset_config)
+    if "image_size" in dataset_config:
+        dataset_config["image_size"] = config_driver.image_size_of(dataset_config)
+    dataset_config.setdefault("size_multiple", pipeline.vae_scale_factor * 2 ** (len(unet.config.block_out_channels) - 1))
     video_dataset = ImageSequenceDataset(**dataset_config, prompt_ids=prompt_ids)
     loader = torch.utils.data.DataLoader(video_dataset, batch_size=batch_size, shuffle=True, num_workers=0, collate_fn=collate_fn)
     log_train_samples(save_path=os.path.join(logdir, "train_samples.gif"), train_dataloader=loader)
@@ -144,10 +149,13 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
     return {"logdir": logdir, "samples": samples, "latents_all_step": latents_all_step}
 
 
-def run_config_file(config: str, **overrides):
-    """test_fatezero.py:254-276: one run for a checkpoint folder that holds `unet/`, otherwise one per `checkpoint_*` child."""
+def run_config_file(config: str, image_size=None, **overrides):
+    """test_fatezero.py:254-276: one run for a checkpoint folder that holds `unet/`, otherwise one per `checkpoint_*` child.
+    `image_size` (an int or a (height, width) pair) replaces `dataset_config.image_size`."""
     cfg = config_driver.load_config(config)
     cfg.update(overrides)
+    if image_size is not None and tuple(image_size) != ():
+        cfg["dataset_config"] = dict(cfg["dataset_config"], image_size=config_driver.image_size_of({"image_size": image_size}))
     root = cfg["pretrained_model_path"]
     if "unet" in os.listdir(root):
         return [test(config=config, **cfg)]
@@ -171,8 +179,10 @@ def run():
     @click.option("--config", type=str, default="config/sample.yml")
     @click.option("--map-dtype", type=click.Choice(list(config_driver.MAP_DTYPES)), default=None,
                   help="storage of the captured self-attention maps (default: editing_config.attention_map_dtype, else fp16)")
-    def _main(config, map_dtype):
-        run_config_file(config, **({} if map_dtype is None else {"map_dtype": map_dtype}))
+    @click.option("--image-size", type=int, nargs=2, default=None, metavar="HEIGHT WIDTH",
+                  help="frame size of a rectangular clip (default: dataset_config.image_size, an int or a [height, width] pair)")
+    def _main(config, map_dtype, image_size):
+        run_config_file(config, image_size=image_size, **({} if map_dtype is None else {"map_dtype": map_dtype}))
 
     _main()
 

@@ -104,6 +104,19 @@ def map_dtype_of(editing_config: Optional[Dict[str, Any]], override: Optional[st
     return value
 
 
+def image_size_of(dataset_config: Optional[Dict[str, Any]]):
+    """`dataset_config.image_size`: an int (square frames, the reference's form) or a `[height, width]` pair (an extension: a clip edited at
+    its own aspect ratio).  Returns the int, or the pair as a tuple of ints; 512 when the key is absent (the dataset's default)."""
+    value = (dataset_config or {}).get("image_size", 512)
+    if isinstance(value, bool):
+        raise ValueError("image_size must be an int or a [height, width] pair, got %r" % (value,))
+    if isinstance(value, int):
+        return value
+    if isinstance(value, (list, tuple)) and len(value) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in value):
+        return int(value[0]), int(value[1])
+    raise ValueError("image_size must be an int or a [height, width] pair, got %r" % (value,))
+
+
 def plan_edits(editing_config: Dict[str, Any], source_prompt: Optional[str]) -> List[Dict[str, Any]]:
     """One dict of pipeline keyword arguments per (editing prompt, seed), in the order the reference runs them."""
     prompts = list(editing_config["editing_prompts"])

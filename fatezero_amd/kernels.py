@@ -241,12 +241,18 @@ def attn_temporal(q, k, v, out, *, batch: int, clip_len: int, heads: int, scale:
 
 # ------------------------------------------------------------------------------------------------------------
 def blend_mask(maps: List[torch.Tensor], alpha: torch.Tensor, th: float, out_hw: Tuple[int, int], *, or_with_first: bool,
-               out: Optional[torch.Tensor] = None):
-    """maps: list of fp16 [P, F, heads, r*r, >=80] views (row stride >= 80); alpha float [P, 80] -> float [P,F,h,w]."""
+               out: Optional[torch.Tensor] = None, map_hw: Optional[Tuple[int, int]] = None):
+    """maps: list of fp16 [P, F, heads, npix, >=80] views (row stride >= 80); alpha float [P, 80] -> float [P,F,h,w].
+    `map_hw=None`: the maps are squares of r*r = npix pixels; a pair (res_h, res_w): res_h rows of res_w pixels (pixel y * res_w + x)."""
     m0 = maps[0]
     P_, F_, heads, npix, _ = m0.shape
-    res = int(round(npix ** 0.5))
-    assert res * res == npix, "the shape of attention map must be a square"
+    if map_hw is None:
+        res = int(round(npix ** 0.5))
+        assert res * res == npix, "the shape of attention map must be a square"
+    else:
+        res_h, res_w = int(map_hw[0]), int(map_hw[1])
+        if res_h <= 0 or res_w <= 0 or res_h * res_w != npix:
+            raise ValueError("map_hw=(%d, %d) does not describe attention maps of %d pixels" % (res_h, res_w, npix))
     for m in maps:
         assert m.shape[:4] == m0.shape[:4] and m.stride() == m0.stride() and m.dtype == torch.float16
         assert m.stride(4) == 1 and m.stride(2) == npix * m.stride(3) and m.stride(1) == heads * m.stride(2)
@@ -255,8 +261,13 @@ def blend_mask(maps: List[torch.Tensor], alpha: torch.Tensor, th: float, out_hw:
         out = torch.empty(P_, F_, h, w, dtype=torch.float32, device=m0.device)
     arr = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
     assert alpha.dtype == torch.float32 and alpha.is_contiguous() and tuple(alpha.shape) == (P_, 80)
-    N.check(N.lib().fz_blend_mask(arr, len(maps), P_, m0.stride(0), F_, heads, res, m0.stride(3), _ptr(alpha), float(th),
-                                  h, w, 1 if or_with_first else 0, _ptr(out), None, _stream(m0)), "fz_blend_mask")
+    if map_hw is None:
+        N.check(N.lib().fz_blend_mask(arr, len(maps), P_, m0.stride(0), F_, heads, res, m0.stride(3), _ptr(alpha), float(th),
+                                      h, w, 1 if or_with_first else 0, _ptr(out), None, _stream(m0)), "fz_blend_mask")
+    else:
+        N.check(N.lib().fz_blend_mask_hw(arr, len(maps), P_, m0.stride(0), F_, heads, res_h, res_w, m0.stride(3), _ptr(alpha),
+                                         float(th), h, w, 1 if or_with_first else 0, _ptr(out), None, _stream(m0)),
+                "fz_blend_mask_hw")
     return out
 
 

@@ -2,7 +2,7 @@
 one clip `images [c, f, h, w]` in [-1, 1] plus the tokenised prompt, which test_fatezero.py:141-196 feeds to the VAE."""
 import os
 from pathlib import Path
-from typing import Dict, Iterable, Optional
+from typing import Dict, Iterable, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -17,12 +17,15 @@ _NO_OFFSET = {"left": 0, "right": 0, "top": 0, "bottom": 0}
 
 class ImageSequenceDataset(Dataset):
     """Item i is the clip that starts at frame `start_sample_frame + stride * i` and takes every `sampling_rate`-th frame,
-    `n_sample_frame` of them (all frames of the folder when negative).  `stride <= 0` means one clip per folder."""
+    `n_sample_frame` of them (all frames of the folder when negative).  `stride <= 0` means one clip per folder.
+    `image_size`: an int (the short side is scaled to it, then a square crop) or a `[height, width]` pair (the frame is scaled until it
+    covers the pair, then cropped to it); each side of a pair must be a multiple of `size_multiple` -- what the VAE and the UNet's
+    downsamplers divide a side by (8 latent pixels times the VAE's factor; the command line passes its models' value)."""
 
     def __init__(self, path: str, prompt_ids: torch.Tensor, prompt: str, start_sample_frame: int = 0, n_sample_frame: int = 8,
-                 sampling_rate: int = 1, stride: int = -1, image_mode: str = "RGB", image_size: int = 512, crop: str = "center",
+                 sampling_rate: int = 1, stride: int = -1, image_mode: str = "RGB", image_size: Union[int, Sequence[int]] = 512, crop: str = "center",
                  class_data_root: Optional[str] = None, class_prompt_ids: Optional[torch.Tensor] = None,
-                 offset: Optional[Dict[str, int]] = None, **args):
+                 offset: Optional[Dict[str, int]] = None, size_multiple: int = 8, **args):
         self.path = path
         self.images = self.get_image_list(path)
         self.n_images = len(self.images)
@@ -36,6 +39,7 @@ class ImageSequenceDataset(Dataset):
         self.stride = stride if stride > 0 else self.n_images + 1
         self.video_len = (self.n_images - self.sequence_length) // self.stride + 1
         self.image_mode, self.image_size = image_mode, image_size
+        self.frame_hw = self._frame_hw(image_size, size_multiple)  # None: the int form
         try:
             self.crop = {"center": T.center_crop, "random": T.random_crop}[crop]
         except KeyError:
@@ -59,11 +63,27 @@ class ImageSequenceDataset(Dataset):
             item["class_prompt_ids"] = self.class_prompt_ids
         return item
 
+    @staticmethod
+    def _frame_hw(image_size, size_multiple):
+        if isinstance(image_size, (int, np.integer)):
+            return None
+        try:
+            height, width = (int(v) for v in image_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"image_size must be an int or a [height, width] pair, got {image_size!r}")
+        for name, side in (("height", height), ("width", width)):
+            if side <= 0 or side % size_multiple != 0:
+                raise ValueError(f"image_size {name} {side} is not a positive multiple of {size_multiple}")
+        return height, width
+
     def transform(self, frames) -> torch.Tensor:
         x = self.tensorize_frames(frames)
         x = T.offset_crop(x, **self.offset)
-        x = T.short_size_scale(x, size=self.image_size)
-        return self.crop(x, height=self.image_size, width=self.image_size)
+        if self.frame_hw is None:
+            x = T.short_size_scale(x, size=self.image_size)
+            return self.crop(x, height=self.image_size, width=self.image_size)
+        height, width = self.frame_hw
+        return self.crop(T.cover_scale(x, height, width), height=height, width=width)
 
     @staticmethod
     def tensorize_frames(frames) -> torch.Tensor:

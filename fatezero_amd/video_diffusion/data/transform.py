@@ -1,6 +1,8 @@
 """Frame geometry of the dataset front-end (reference: video_diffusion/data/transform.py): crop a fixed border, scale the
-short side with an anti-aliased bilinear filter, crop to a square.  All functions take a 4-D float tensor whose last two
+short side with an anti-aliased bilinear filter (or, for a rectangular target, scale until the frame covers it), crop to the target.
+All functions take a 4-D float tensor whose last two
 dimensions are (height, width) -- the dataset hands over [c, f, h, w] -- and return a view / a resized copy."""
+import math
 import random
 
 import torch
@@ -26,6 +28,20 @@ def short_size_scale(images: torch.Tensor, size: int) -> torch.Tensor:
     else:
         target = (int(size / w * h), size)
     return F.interpolate(images, size=target, mode="bilinear", antialias=True)
+
+
+def resize_by(images: torch.Tensor, factor: float) -> torch.Tensor:
+    """Resize both sides by `factor` with the filter of `short_size_scale`; a side becomes ceil(side * factor - 1e-6), so that a
+    factor chosen to reach a target side never falls one pixel short of it."""
+    h, w = images.shape[-2:]
+    target = (max(1, math.ceil(h * factor - 1e-6)), max(1, math.ceil(w * factor - 1e-6)))
+    return F.interpolate(images, size=target, mode="bilinear", antialias=True)
+
+
+def cover_scale(images: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """Resize by max(height / h, width / w): the smallest frame of the same aspect ratio that covers (height, width)."""
+    h, w = images.shape[-2:]
+    return resize_by(images, max(height / h, width / w))
 
 
 def random_short_side_scale(images: torch.Tensor, size_min: int, size_max: int) -> torch.Tensor:

@@ -140,6 +140,7 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
             bf, c, h, w = init.shape
             latents = init.reshape(batch_size, bf // batch_size, c, h, w).permute(0, 2, 1, 3, 4)  # (b f) c h w -> b c f h w
         self.store_controller.expected_steps = len(self.scheduler.timesteps) if store_attention else None
+        self.store_controller.latent_hw = tuple(latents.shape[-2:])  # the clip's own geometry: map sizes of every level follow from it
         ddim_latents_all_step = self.ddim_clean2noisy_loop(latents, text_embeddings, self.store_controller)
         if store_attention and (save_path is not None):
             os.makedirs(save_path + "/cross_attention", exist_ok=True)
@@ -255,6 +256,19 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
                          callback_steps: Optional[int] = 1, controller=None, **args):
         """CFG DDIM denoise loop (p2p_ddim_spatial_temporal.py:261-435). `output_type='latent'` (extension) returns the
         final latents without a VAE."""
+        # the frame size is the one of the latents / images handed in; an explicit height / width may only repeat it
+        if latents is not None:
+            given = (latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor)
+        elif image is not None:
+            given = tuple(image.shape[-2:])
+        else:
+            given = None
+        if given is not None:
+            for name, asked, have in (("height", height, given[0]), ("width", width, given[1])):
+                if asked is not None and asked != have:
+                    raise ValueError(f"`{name}`={asked} contradicts the {'latents' if latents is not None else 'images'} handed in, "
+                                     f"which are {given[0]} x {given[1]} pixels (height x width)")
+            height, width = given
         sample_size = getattr(self.unet.config, "sample_size", None) or 64
         height = height or sample_size * self.vae_scale_factor
         width = width or sample_size * self.vae_scale_factor
@@ -271,6 +285,8 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
             latents = self.prepare_latents_ddim_inverted(image, batch_size, num_images_per_prompt, text_embeddings,
                                                          store_attention=False, generator=generator)[-1]
         latents_dtype = latents.dtype
+        if isinstance(controller, attention_util.AttentionControl):
+            controller.latent_hw = tuple(latents.shape[-2:])
         shard = self.frame_shard
         if shard is not None:
             latents = shard.local(latents, 2).contiguous()

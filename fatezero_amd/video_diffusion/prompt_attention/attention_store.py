@@ -22,6 +22,7 @@ back (FZ_ATTN_INJECT8).  Cross maps stay fp16.  Every reference-shaped reader (`
 sum with `accumulate_self`) sees fp16 tensors dequantised exactly from the bytes, built when they are read.
 """
 import abc
+import math
 import os
 from typing import Dict, List, Optional
 
@@ -33,6 +34,21 @@ from ..models.attention import AttnPlan
 KEYS = ("down_cross", "mid_cross", "up_cross", "down_self", "mid_self", "up_self")
 MAP_DTYPES = ("fp16", "e5m2")  # storage of the captured self-attention maps
 MAX_CONTROLLED_TOKENS = 32 ** 2  # attention_store.py:83, attention_util.py:104
+
+
+def map_hw(lq: int, extent=None):
+    """(h, w) of an attention level with `lq` query tokens (token y * w + x), given an extent (H, W) of the same aspect ratio (the latent
+    size, or the size a mask is resized to): h = round(sqrt(lq * H / W)), w = lq // h, with h * w == lq and h * W == w * H required.
+    `extent=None` (a controller nobody told the latent size): the reference's square, int(sqrt(lq)) on both sides."""
+    if extent is None:
+        h = int(math.sqrt(lq))
+        return h, h
+    H, W = int(extent[0]), int(extent[1])
+    h = int(round(math.sqrt(lq * H / W))) if H > 0 and W > 0 else 0
+    w = lq // h if h > 0 else 0
+    if h <= 0 or h * w != lq or h * W != w * H:
+        raise ValueError(f"an attention map of lq={lq} tokens is no (h, w) grid with the aspect ratio of (H, W)=({H}, {W})")
+    return h, w
 
 
 class AttentionControl(abc.ABC):

@@ -20,14 +20,13 @@ The reference's tensor protocol (`forward(attn, is_cross, place)`, `replace_cros
 import abc
 from typing import Dict, List, Optional, Tuple, Union
 
-import numpy as np
 import torch
 
 from ... import kernels as K
 from ..models.attention import AttnPlan
 from . import ptp_utils, seq_aligner
 from .attention_register import register_attention_control  # noqa: F401  (re-exported like the reference)
-from .attention_store import KEYS, MAX_CONTROLLED_TOKENS, AttentionControl, AttentionStore, CapturedMap
+from .attention_store import KEYS, MAX_CONTROLLED_TOKENS, AttentionControl, AttentionStore, CapturedMap, map_hw
 from .spatial_blend import SpatialBlender
 
 MAX_WORDS = 77
@@ -128,6 +127,16 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
                 bool(self.track_cross_attention), self.visualize_res, self.map_dtype,
                 getattr(self.additional_attention_store, "map_dtype", "fp16"))
 
+    def _is_visualize_level(self, lq):
+        """The level `show_cross_attention(..., visualize_res, ...)` renders: the one whose longer side is `visualize_res`."""
+        extent = getattr(self, "latent_hw", None)
+        if extent is None or extent[0] == extent[1]:
+            return lq == self.visualize_res ** 2
+        try:
+            return max(map_hw(lq, extent)) == self.visualize_res
+        except ValueError:
+            return False
+
     def plan_controlled(self, is_cross, place, n_ctrl, clip_len, heads, lq, lk, device) -> AttnPlan:
         if lq > MAX_CONTROLLED_TOKENS:
             return AttnPlan(0)
@@ -142,7 +151,7 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         if is_cross:
             mapper_t, coef = self.cross_constants(self.cur_step, device)
             plan.mode, plan.p, plan.mapper_t, plan.coef = K.FZ_ATTN_INJECT, base.storage, mapper_t, coef
-            if self.track_cross_attention or (self.visualize_res is not None and lq == self.visualize_res ** 2):
+            if self.track_cross_attention or (self.visualize_res is not None and self._is_visualize_level(lq)):
                 plan.cur_out = self.new_slot(key, n_ctrl, heads, lq, lk, True, device).storage
             return plan
         if self.save_self_attention:  # only outside the 'swap' flow of the reference's validation loop
@@ -150,9 +159,9 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         if self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]:
             plan.mode, plan.p = K.self_mode_for(K.FZ_ATTN_INJECT, base.storage), base.storage  # (INJECT8 over an E5M2 map)
             if self.attention_blend is not None:
-                h = int(np.sqrt(lq))
-                mask = self.attention_blend(target_h=h, target_w=h, attention_store=step_maps, step_in_store=sis)
-                plan.row_mask = mask[0].reshape(mask.shape[1], h * h).contiguous()  # [F, Lq]: 1 keeps the live attention
+                h, w = map_hw(lq, getattr(self, "latent_hw", None))
+                mask = self.attention_blend(target_h=h, target_w=w, attention_store=step_maps, step_in_store=sis)
+                plan.row_mask = mask[0].reshape(mask.shape[1], h * w).contiguous()  # [F, Lq]: 1 keeps the live attention
         return plan
 
     # ---------------------------------------------------------------------------------------------------
@@ -191,11 +200,11 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
                 else:
                     reshaped_mask = None
                     if self.attention_blend is not None:
-                        h = int(np.sqrt(attn.shape[-2]))
-                        mask = self.attention_blend(target_h=h, target_w=h,
+                        h, w = map_hw(attn.shape[-2], getattr(self, "latent_hw", None))
+                        mask = self.attention_blend(target_h=h, target_w=w,
                                                     attention_store=self.additional_attention_store.maps_of_step(sis),
                                                     step_in_store=sis)
-                        reshaped_mask = mask.permute(1, 0, 2, 3).reshape(mask.shape[1], mask.shape[0], h * h)[..., None].to(attn.dtype)
+                        reshaped_mask = mask.permute(1, 0, 2, 3).reshape(mask.shape[1], mask.shape[0], h * w)[..., None].to(attn.dtype)
                     attn = self.replace_self_attention(attn_base, attn, reshaped_mask)
                 attn = attn.reshape(self.batch_size * clip_length, *attn.shape[2:])
         return attn

@@ -25,7 +25,7 @@ import torch
 
 from ... import kernels as K
 from . import ptp_utils
-from .attention_store import CapturedMap
+from .attention_store import CapturedMap, map_hw
 
 
 def mask_grid_image(mask: np.ndarray, nrow: int = 8, padding: int = 2) -> np.ndarray:
@@ -192,15 +192,17 @@ class SpatialBlender:
         return list(store_dict["down_cross"][2:4]) + list(store_dict["up_cross"][:3])
 
     def mask_from_storage(self, maps5: List[torch.Tensor], target_h, target_w):
-        """maps5: fp16 storages [P, F, heads, r*r, 80]. Returns float mask [P, F, h, w] of 0/1."""
+        """maps5: fp16 storages [P, F, heads, npix, 80], npix pixels of the aspect ratio of the target. Returns float mask [P, F, h, w] of 0/1."""
         n_prompts = maps5[0].shape[0]
         res = {m.shape[3] for m in maps5}
         if len(res) != 1:  # the reference's torch.cat(dim=1) raises on this (SURVEY App. A, 256^2 inputs)
             raise RuntimeError(f"blend-mask maps have different resolutions {sorted(res)}: blend_words needs the "
                                "512^2 list layout (five 16x16 cross maps)")
         alpha = self._alpha80(n_prompts, maps5[0].device)
+        # a square target keeps the square inference of the kernel layer; any other takes the maps' (h, w) from its aspect ratio
+        hw = None if target_h == target_w else map_hw(maps5[0].shape[3], (target_h, target_w))
         return K.blend_mask(maps5, alpha, float(self.th[0]), (target_h, target_w),
-                            or_with_first=(self.prompt_choose == "both"))
+                            or_with_first=(self.prompt_choose == "both"), map_hw=hw)
 
     def _dump(self, mask, step_in_store, cache_key):
         """spatial_blend.py:43-55: one PNG per get_mask call (the last prompt's mask when there are two), numbered by

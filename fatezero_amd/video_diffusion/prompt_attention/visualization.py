@@ -14,21 +14,38 @@ import torch
 from PIL import Image, ImageDraw, ImageFont
 
 
+def _level_hw(attention_store, lq: int, res: int):
+    """(h, w) of a stored map with `lq` query tokens when it is the level `res` names, else None.  A store that knows the latent extent
+    (`latent_hw`, set by the pipeline) of a rectangular clip: the level whose longer side is `res`; any other: the res x res square."""
+    from .attention_store import map_hw
+    extent = getattr(attention_store, "latent_hw", None)
+    if extent is None or extent[0] == extent[1]:
+        return (res, res) if lq == res ** 2 else None
+    try:
+        h, w = map_hw(lq, extent)
+    except ValueError:
+        return None
+    return (h, w) if max(h, w) == res else None
+
+
 def aggregate_attention(prompts, attention_store, res: int, from_where: List[str], is_cross: bool, select: int, to_cpu=True):
-    """Mean over (layers of `from_where` with res*res query tokens) x heads of the step-averaged maps
-    -> [frames, res, res, tokens] (visualization.py:14-32)."""
+    """Mean over (layers of `from_where` at the level `res`: res*res query tokens, or h*w with the longer side `res` on a rectangular
+    clip) x heads of the step-averaged maps -> [frames, h, w, tokens] (visualization.py:14-32)."""
     out = []
     maps = attention_store.get_average_attention()
-    num_pixels = res ** 2
     kind = "cross" if is_cross else "self"
     for location in from_where:
         for item in maps[f"{location}_{kind}"]:
             item = item.float()
-            if item.dim() == 3 and item.shape[1] == num_pixels:
-                out.append(item.reshape(len(prompts), -1, res, res, item.shape[-1])[select])
-            elif item.dim() == 4 and item.shape[2] == num_pixels:
-                t = item.shape[0]
-                out.append(item.reshape(len(prompts), t, -1, res, res, item.shape[-1])[select])
+            if item.dim() == 3:
+                hw = _level_hw(attention_store, item.shape[1], res)
+                if hw is not None:
+                    out.append(item.reshape(len(prompts), -1, hw[0], hw[1], item.shape[-1])[select])
+            elif item.dim() == 4:
+                hw = _level_hw(attention_store, item.shape[2], res)
+                if hw is not None:
+                    t = item.shape[0]
+                    out.append(item.reshape(len(prompts), t, -1, hw[0], hw[1], item.shape[-1])[select])
     if not out:
         raise ValueError(f"no stored {kind} map with {res}x{res} query tokens under {from_where}")
     out = torch.cat(out, dim=-4)
@@ -133,7 +150,9 @@ def show_cross_attention(tokenizer, prompts, attention_store, res: int, from_whe
                 m = maps[j, :, :, i]
                 m = 255 * m / m.max().clamp_min(1e-20)
                 img = m.unsqueeze(-1).expand(*m.shape, 3).numpy().astype(np.uint8)
-                img = np.array(Image.fromarray(img).resize((256, 256)))
+                mh, mw = m.shape  # the longer side of the tile is 256 pixels: 256 x 256 for a square map
+                size = (256, 256) if mh == mw else (max(1, round(256 * mw / max(mh, mw))), max(1, round(256 * mh / max(mh, mw))))
+                img = np.array(Image.fromarray(img).resize(size))
                 tiles.append(text_under_image(img, _decode_one(tokenizer, tokens[i])))
             if save_path is not None:
                 view_images(np.stack(tiles, axis=0), save_path=save_path)

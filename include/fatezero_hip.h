@@ -140,6 +140,14 @@ int fz_blend_mask(const void* const* maps, int n_maps, int n_prompts, int64_t pr
                   int heads, int res, int64_t p_row_stride, const float* alpha, float th, int out_h, int out_w,
                   int or_with_first, float* out, float* scratch, void* stream);
 
+/* The same mask from rectangular maps [P][F][heads][res_h*res_w][p_row_stride] (pixel index y * res_w + x): the 3x3 max-pool
+ * runs on the res_h x res_w grid and the nearest resize scales rows by res_h / out_h and columns by res_w / out_w.
+ * Domain: res_h, res_w > 0 and res_h * res_w <= 1600, else FZ_ERR_BAD_ARG.  fz_blend_mask(res) is this entry with
+ * res_h = res_w = res. */
+int fz_blend_mask_hw(const void* const* maps, int n_maps, int n_prompts, int64_t prompt_stride, int frames, int heads,
+                     int res_h, int res_w, int64_t p_row_stride, const float* alpha, float th,
+                     int out_h, int out_w, int or_with_first, float* out, float* scratch, void* stream);
+
 /* GroupNorm (+SiLU) on token-major activations x[n][tokens][C] (resnet.py:338-339,369,384; attention.py:110;
  * unet_3d_condition.py:439-440).  span = number of consecutive frames sharing statistics: F for the 5-D
  * ResNet norms (stats over C/G x F x H x W), 1 for the per-frame transformer norm.
