@@ -16,7 +16,7 @@ FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8 = 3, 4  # fz_attn_self: the map as E5M2 bytes 
 FZ_MAX_KV_SLOTS = 4
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80
-FZ_TEMPORAL_MAX_FRAMES = 256
+FZ_TEMPORAL_MAX_FRAMES = 512
 
 
 class FzAttnSelfDesc(C.Structure):

@@ -2,7 +2,8 @@
 // diffusers CrossAttention.forward applied on '(b d) f c' (attention.py:327-337 of the reference).
 //
 // Up to 64 frames the sequence length is the clip length (8..32 in the reference's configs), so this is a bandwidth problem, not an
-// MFMA one (longer clips, up to FZ_TEMPORAL_MAX_FRAMES, take attn_temporal_long_kernel further down, which is an MFMA one): q, k, v stay
+// MFMA one (longer clips take attn_temporal_long_kernel, up to 256 frames, and attn_temporal_stream_kernel, up to
+// FZ_TEMPORAL_MAX_FRAMES, further down, which are MFMA ones): q, k, v stay
 // in their native token-major layout [(b f)][token][channel] (no '(b f) d c -> (b d) f c' rearrange is ever
 // materialised); one thread owns one (token, head, query frame), the F key/value rows of its pixel are shared
 // through L1 by the F threads of that pixel, and scores live in LDS.
@@ -11,7 +12,8 @@
 #include <stdlib.h>
 
 #define TMAXF 64                                 // the one-thread-per-query-frame kernels below serve clips up to here ...
-#define TLONG_MAXF FZ_TEMPORAL_MAX_FRAMES        // ... attn_temporal_long_kernel (matrix pipe) the longer ones
+#define TLONG_MAXF 256                           // ... attn_temporal_long_kernel (matrix pipe, whole score rows in registers) up to here ...
+#define TSTREAM_MAXF FZ_TEMPORAL_MAX_FRAMES      // ... attn_temporal_stream_kernel (matrix pipe, keys walked in chunks) the longer ones
 #define TTHREADS 256
 
 struct TemporalArgs {
@@ -232,7 +234,7 @@ FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_lds_kernel(TemporalArgs
 //   softmax       over the keys of a query = over the lane's NT x 16 registers and the lane pair (l, l ^ 32).  The WHOLE row is in
 //                 registers (NT <= 8 tiles x 16 fp32), so it is the exact two-pass softmax of the reference: P is normalised, THEN
 //                 rounded to fp16, then multiplied -- an online softmax could only round the un-normalised P.  That register file of
-//                 scores is what sets FZ_TEMPORAL_MAX_FRAMES = 8 x 32.
+//                 scores is what ends this kernel at 8 x 32 = 256 frames (attn_temporal_stream_kernel below takes over there).
 //   O^T = V^T P^T B = P^T [16 keys][32 queries] is the C fragment above as it lies (registers 8kc..8kc+7 of tile t -> half8), i.e.
 //                 contraction slot (kc, hi, e) of tile t is key 32t + 16kc + 8(e >> 2) + 4hi + (e & 3): bits 2 and 3 of the key's
 //                 offset inside its group of 16 are swapped against the natural order.  A = V^T [32 ch][16 keys] has to supply
@@ -397,13 +399,243 @@ static int tlong_launch(const TemporalLongArgs& a0, int batch, void* stream) {
     return FZ_ERR_BAD_ARG;
 }
 
+// Clips beyond 256 frames (kv_frames or q_frames > TLONG_MAXF): the same two transposed MFMA products, but nothing in the kernel's
+// register or LDS footprint grows with the clip -- the keys are walked in CHUNKS of TSTREAM_CHUNK = 256 frames by a run-time loop.
+// The numeric contract is unchanged (P = half(exp(s - m) * (1 / l)) with m and l over ALL keys in fp32, O accumulated in fp32 and
+// rounded once), which an online softmax cannot meet (it could only round the un-normalised P and rescale O), so the keys are
+// walked TWICE:
+//   sweep 1   S^T tile by tile (32 keys x 32 queries, K fragments straight from global rows as above): every lane keeps a running
+//             maximum and a rescaled running sum over the keys it holds; the lane pair (l, l ^ 32) is combined once at the end.
+//             No LDS, no barrier.
+//   sweep 2   per chunk: V of the chunk is staged transposed (tlong_key_pos swap, zero-filled beyond the clip) between two
+//             barriers, then every score tile of the chunk is RECOMPUTED by the same function (the same MFMA chain; the compiler may
+//             contract the scale into the subtraction of m on one side only: at most an fp32 ulp of a score, five orders of
+//             magnitude below the fp16 rounding of P), turned into the final fp16 P with the m and 1 / l of sweep 1, and
+//             multiplied into O^T.
+//             The O^T accumulators (16 fp32 per 32-channel tile) stay in registers across the chunks.
+// Q K^T twice is the cheap side of the trade: per (token, head) the whole problem is F x F x d, and the alternative -- keeping F
+// scores per query somewhere -- is what tied the long kernel's footprint to the clip length.
+// One workgroup = one (batch element, token, group of HG heads, group of four 32-query tiles): wave w owns query tile 4 qg + w for
+// all HG heads (a wave whose tile lies beyond q_frames only helps staging).  The Q fragments of the wave's tile are loaded once and
+// kept in registers for both sweeps.  HG * CT <= 5 accumulator tiles (CT = channel tiles of a head): 80 fp32 at head_dim 160.
+#define TSTREAM_CHUNK 256
+#define TSTREAM_LDV (TSTREAM_CHUNK + 8)  // halves between channel rows of Vt: 132 dwords, rows 4 banks apart
+struct TemporalStreamArgs {
+    const half_t *q, *k, *v;
+    half_t* o;
+    int F, Fq, tokens, heads, dh;
+    int ngroups, nqg;  // head groups per token, groups of four query tiles per (token, head group)
+    int64_t in_stride, q_stride, out_stride;
+    float scale;
+};
+
+// scores of key tile `t` (32 keys) against the wave's 32 queries, scaled, keys beyond the clip at -1e30: lane (i, hi) holds for
+// query i the keys 32t + 8g + 4hi + r in register 4g + r.  kcol: column `8 hi` of the head in frame 0's row of this token.
+template <int CT>
+FZ_DEVICE f32x16 tstream_scores(const half_t* kcol, int64_t kv_frame, int t, int i, int hi, int F, int dh, float scale,
+                                const half8_t (&qfr)[2 * CT]) {
+    f32x16 s = fz_zero_f16v();
+    const int key = 32 * t + i;
+    const half_t* krow = kcol + (key < F ? key : 0) * kv_frame;
+#pragma unroll
+    for (int cs = 0; cs < 2 * CT; ++cs)
+        if (16 * cs < dh) {
+            const half8_t kfrag = (key < F && 16 * cs + 8 * hi < dh) ? fz_ld_h8(krow + 16 * cs) : fz_zero_h8();
+            s = fz_mfma_32x32x16_f16(kfrag, qfr[cs], s);
+        }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int kr = 32 * t + 8 * (r >> 2) + 4 * hi + (r & 3);
+        s[r] = kr < F ? s[r] * scale : -1e30f;
+    }
+    return s;
+}
+
+template <int HG, int CT>
+FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_stream_kernel(TemporalStreamArgs a) {
+    FZ_DYN_SMEM(raw);
+    half_t* Vt = reinterpret_cast<half_t*>(raw);  // [HG][dh][TSTREAM_LDV]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y;
+    int bx = blockIdx.x;
+    const int qg = bx % a.nqg;
+    bx /= a.nqg;
+    const int h0 = (bx % a.ngroups) * HG;
+    const int tok = bx / a.ngroups;
+    const int F = a.F, dh = a.dh;
+    const int nvec = dh >> 3;
+    const int lane = tid & 63, wave = fz_uniform(tid >> 6);
+    const int i = lane & 31, hi = lane >> 5;
+    const int ntiles = (F + 31) >> 5, nchunks = (F + TSTREAM_CHUNK - 1) / TSTREAM_CHUNK;
+    const int qt = qg * (TTHREADS / 64) + wave;
+    const bool active = qt < ((a.Fq + 31) >> 5);  // wave-uniform
+    const int qf = qt * 32 + i;
+    const bool qok = active && qf < a.Fq;
+    const int64_t kv_frame = (int64_t)a.tokens * a.in_stride;  // halves between the same token of consecutive frames
+    const int64_t qo_row = ((int64_t)b * a.Fq + (qok ? qf : 0)) * a.tokens + tok;
+    const half_t* qrow = a.q + qo_row * a.q_stride + h0 * dh;
+    const half_t* kcol = a.k + ((int64_t)b * F * a.tokens + tok) * a.in_stride + h0 * dh + 8 * hi;  // frame 0 of this batch element
+    const half_t* vcol = a.v + ((int64_t)b * F * a.tokens + tok) * a.in_stride + h0 * dh;
+    half8_t qfr[HG][2 * CT];
+#pragma unroll
+    for (int hl = 0; hl < HG; ++hl)
+#pragma unroll
+        for (int cs = 0; cs < 2 * CT; ++cs) {
+            const int ch = 16 * cs + 8 * hi;
+            qfr[hl][cs] = (qok && ch < dh) ? fz_ld_h8(qrow + hl * dh + ch) : fz_zero_h8();
+        }
+    // ---- sweep 1: m and 1 / l of every query over ALL keys
+    float mx[HG], inv[HG];
+#pragma unroll
+    for (int hl = 0; hl < HG; ++hl) mx[hl] = 0.0f, inv[hl] = 0.0f;
+    if (active) {
+#pragma unroll
+        for (int hl = 0; hl < HG; ++hl) {
+            float m = -1e30f, l = 0.0f;
+            for (int t = 0; t < ntiles; ++t) {
+                const f32x16 s = tstream_scores<CT>(kcol + hl * dh, kv_frame, t, i, hi, F, dh, a.scale, qfr[hl]);
+                float mn = m;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mn = fmaxf(mn, s[r]);
+                float ts = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kr = 32 * t + 8 * (r >> 2) + 4 * hi + (r & 3);
+                    ts += kr < F ? __builtin_expf(s[r] - mn) : 0.0f;
+                }
+                l = l * __builtin_expf(m - mn) + ts;
+                m = mn;
+            }
+            const float mall = fz_pair_max32(m);
+            l *= __builtin_expf(m - mall);
+            l += fz_shfl_xor(l, 32);
+            mx[hl] = mall;
+            inv[hl] = 1.0f / l;
+        }
+    }
+    // ---- sweep 2: chunk by chunk, V staged transposed, scores recomputed, O^T accumulated
+    f32x16 acc[HG][CT];
+#pragma unroll
+    for (int hl = 0; hl < HG; ++hl)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[hl][ct] = fz_zero_f16v();
+    for (int c = 0; c < nchunks; ++c) {
+        const int k0 = c * TSTREAM_CHUNK;
+        const int ntc = ntiles - c * (TSTREAM_CHUNK / 32) < TSTREAM_CHUNK / 32 ? ntiles - c * (TSTREAM_CHUNK / 32) : TSTREAM_CHUNK / 32;
+        const int ckeys = ntc * 32;  // key positions of this chunk (whole tiles; beyond the clip zero-filled)
+        if (c) __syncthreads();      // every wave has read the previous chunk's V
+        for (int id = tid; id < HG * nvec * ckeys; id += TTHREADS) {
+            const int key = id % ckeys, cv = (id / ckeys) % nvec, hl = id / (ckeys * nvec);
+            half8_t vv = fz_zero_h8();
+            if (k0 + key < F) vv = fz_ld_h8(vcol + (k0 + key) * kv_frame + hl * dh + cv * 8);
+            half_t* dst = Vt + ((size_t)hl * dh + cv * 8) * TSTREAM_LDV + tlong_key_pos(key);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dst[(size_t)e * TSTREAM_LDV] = vv[e];
+        }
+        __syncthreads();
+        if (!active) continue;
+#pragma unroll
+        for (int hl = 0; hl < HG; ++hl)
+            for (int t = 0; t < ntc; ++t) {
+                const int tg = c * (TSTREAM_CHUNK / 32) + t;
+                const f32x16 s = tstream_scores<CT>(kcol + hl * dh, kv_frame, tg, i, hi, F, dh, a.scale, qfr[hl]);
+                half8_t p[2];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kr = 32 * tg + 8 * (r >> 2) + 4 * hi + (r & 3);
+                    const float e = kr < F ? __builtin_expf(s[r] - mx[hl]) : 0.0f;
+                    p[r >> 3][r & 7] = (half_t)(e * inv[hl]);  // P is normalised, THEN cast to fp16, then multiplied
+                }
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+                    if (32 * ct < dh) {
+                        const bool chok = 32 * ct + i < dh;
+                        const half_t* vrow = Vt + ((size_t)hl * dh + (chok ? 32 * ct + i : 0)) * TSTREAM_LDV + 32 * t + 8 * hi;
+#pragma unroll
+                        for (int kc = 0; kc < 2; ++kc) {
+                            const half8_t vfrag = chok ? fz_ld_h8(vrow + 16 * kc) : fz_zero_h8();
+                            acc[hl][ct] = fz_mfma_32x32x16_f16(vfrag, p[kc], acc[hl][ct]);
+                        }
+                    }
+            }
+    }
+    if (!qok) return;
+    half_t* orow = a.o + qo_row * a.out_stride + h0 * dh;
+#pragma unroll
+    for (int hl = 0; hl < HG; ++hl)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ch = 32 * ct + 8 * g + 4 * hi;
+                if (ch < dh) {
+                    half4_t ov;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ov[r] = (half_t)acc[hl][ct][4 * g + r];
+                    *reinterpret_cast<half4_t*>(orow + hl * dh + ch) = ov;
+                }
+            }
+}
+
+// heads per workgroup of the streaming kernel: the long kernel's rule (the largest divisor of `heads` whose transposed V chunk fits
+// 64 KB; a single head beyond that -- head_dim 128..160 -- takes the opt-in path, 82.5 KB at the most) with one more bound: the
+// group's O^T accumulators, HG x CT tiles of 16 fp32, are capped at 5 tiles.  head_dim > 160 is not served by this form.
+static int tstream_launch(const TemporalStreamArgs& a0, int batch, void* stream) {
+    TemporalStreamArgs a = a0;
+    const int ct = (a.dh + 31) / 32;
+    if (ct > 5) return FZ_ERR_UNSUPPORTED;
+    const size_t per_head = (size_t)a.dh * TSTREAM_LDV * sizeof(half_t);
+    int hg = 1;
+    for (int g = a.heads; g >= 1; --g)
+        if (a.heads % g == 0 && g * per_head <= 64 * 1024 && g * ct <= 5) {
+            hg = g;
+            break;
+        }
+    a.ngroups = a.heads / hg;
+    a.nqg = ((a.Fq + 31) / 32 + TTHREADS / 64 - 1) / (TTHREADS / 64);
+    const size_t lds = hg * per_head;
+    if (lds > 160 * 1024 || (int64_t)a.tokens * a.ngroups * a.nqg > 0x7fffffff || batch > 65535) return FZ_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)(a.tokens * a.ngroups * a.nqg), batch), block(TTHREADS);
+    auto launch = [&](auto kern) -> int {
+#ifndef FZ_EMU
+        if (lds > 64 * 1024) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return FZ_ERR_LAUNCH;
+        }
+#endif
+        FZ_LAUNCH(kern, grid, block, lds, stream, a);
+        return fz_last_launch_status();
+    };
+    switch (hg * 8 + ct) {
+        case 1 * 8 + 1: return launch(attn_temporal_stream_kernel<1, 1>);
+        case 1 * 8 + 2: return launch(attn_temporal_stream_kernel<1, 2>);
+        case 1 * 8 + 3: return launch(attn_temporal_stream_kernel<1, 3>);
+        case 1 * 8 + 4: return launch(attn_temporal_stream_kernel<1, 4>);
+        case 1 * 8 + 5: return launch(attn_temporal_stream_kernel<1, 5>);
+        case 2 * 8 + 1: return launch(attn_temporal_stream_kernel<2, 1>);
+        case 2 * 8 + 2: return launch(attn_temporal_stream_kernel<2, 2>);
+        case 3 * 8 + 1: return launch(attn_temporal_stream_kernel<3, 1>);
+        case 4 * 8 + 1: return launch(attn_temporal_stream_kernel<4, 1>);
+        case 5 * 8 + 1: return launch(attn_temporal_stream_kernel<5, 1>);
+    }
+    return FZ_ERR_BAD_ARG;
+}
+
 extern "C" int fz_attn_temporal_ex(const void* q, const void* k, const void* v, void* o, int batch, int q_frames,
                                    int kv_frames, int tokens, int heads, int head_dim, int64_t q_row_stride,
                                    int64_t kv_row_stride, int64_t o_row_stride, float scale, void* stream) {
-    if (!q || !k || !v || !o || batch <= 0 || q_frames <= 0 || kv_frames <= 0 || kv_frames > TLONG_MAXF ||
-        q_frames > TLONG_MAXF || tokens <= 0 || heads <= 0 || head_dim <= 0)
+    if (!q || !k || !v || !o || batch <= 0 || q_frames <= 0 || kv_frames <= 0 || kv_frames > TSTREAM_MAXF ||
+        q_frames > TSTREAM_MAXF || tokens <= 0 || heads <= 0 || head_dim <= 0)
         return FZ_ERR_BAD_ARG;
     if ((head_dim & 7) || (q_row_stride & 7) || (kv_row_stride & 7) || (o_row_stride & 7)) return FZ_ERR_BAD_ARG;
+    if (kv_frames > TLONG_MAXF || q_frames > TLONG_MAXF) {  // beyond 256 frames: the streaming kernel.  Up to there nothing below has changed.
+        TemporalStreamArgs t;
+        t.q = (const half_t*)q; t.k = (const half_t*)k; t.v = (const half_t*)v; t.o = (half_t*)o;
+        t.F = kv_frames; t.Fq = q_frames; t.tokens = tokens; t.heads = heads; t.dh = head_dim;
+        t.ngroups = t.nqg = 0;
+        t.in_stride = kv_row_stride; t.q_stride = q_row_stride; t.out_stride = o_row_stride; t.scale = scale;
+        return tstream_launch(t, batch, stream);
+    }
     if (kv_frames > TMAXF || q_frames > TMAXF) {  // long clips: the matrix-pipe kernel.  Up to TMAXF nothing below has changed.
         TemporalLongArgs l;
         l.q = (const half_t*)q; l.k = (const half_t*)k; l.v = (const half_t*)v; l.o = (half_t*)o;

@@ -221,7 +221,9 @@ def attn_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
 def attn_temporal(q, k, v, out, *, batch: int, clip_len: int, heads: int, scale: Optional[float] = None,
                   kv_frames: Optional[int] = None):
     """q,out: [B*clip_len, tokens, >=C]; k,v: [B*kv_frames, tokens, >=C] token-major views (kv_frames defaults to clip_len;
-    it is larger when the clip is frame-sharded and k / v were all-gathered).  Neither may exceed TEMPORAL_MAX_FRAMES."""
+    it is larger when the clip is frame-sharded and k / v were all-gathered).  Neither may exceed TEMPORAL_MAX_FRAMES (512): the
+    larger of the two picks the kernel -- up to 64 one thread per query frame, up to 256 whole score rows in registers, beyond that
+    the streaming kernel (keys in chunks of 256, head_dim <= 160).  A longer clip is a ValueError that names the limit."""
     _, tokens, c = q.shape
     d_head = c // heads
     kv_frames = clip_len if kv_frames is None else kv_frames

@@ -113,21 +113,26 @@ typedef struct FzAttnCrossDesc {
 int fz_attn_cross(const FzAttnCrossDesc* desc, const void* q, const void* k, const void* vt, void* o,
                   void* p, const void* mapper_t, const float* coef, void* cur_out, void* stream);
 
-/* Longest clip temporal attention serves: 8 key tiles of 32 frames, whose scores the long-clip kernel keeps in registers as
- * whole rows (the exact softmax of the reference: P is normalised before it is rounded to fp16). */
-#define FZ_TEMPORAL_MAX_FRAMES 256
+/* Longest clip temporal attention serves.  Up to 256 frames (8 key tiles of 32) the long-clip kernel keeps the scores in registers
+ * as whole rows; beyond, the streaming kernel walks the keys in chunks of 256 and its footprint no longer depends on the clip, with
+ * the same exact softmax of the reference (P is normalised over ALL keys before it is rounded to fp16).  512 is therefore what
+ * the tests cover, not what the kernel can do: the long-clip tests are parameterised by this constant and their full CPU reference
+ * grows with its square (1024 would need tens of GB of host memory there). */
+#define FZ_TEMPORAL_MAX_FRAMES 512
 
 /* Temporal attention over frames (un-patched CrossAttention.forward, attention.py:327-337):
  * q,k,v,o: [B*F][tokens][channels] (row stride given); each (b, token, head) attends over its F frames.
  * Domain: 1 <= clip_len <= FZ_TEMPORAL_MAX_FRAMES, head_dim % 8 == 0, row strides % 8 == 0 (elements); FZ_ERR_BAD_ARG outside it.
- * Clips of up to 64 frames run the one-thread-per-query-frame kernels, longer ones the matrix-pipe kernel (csrc/attn_temporal.hip). */
+ * Clips of up to 64 frames run the one-thread-per-query-frame kernels, up to 256 the matrix-pipe kernel with whole score rows in
+ * registers, longer ones the streaming matrix-pipe kernel (csrc/attn_temporal.hip; head_dim <= 160 there, FZ_ERR_UNSUPPORTED beyond). */
 int fz_attn_temporal(const void* q, const void* k, const void* v, void* o, int batch, int clip_len,
                      int tokens, int heads, int head_dim, int64_t qkv_row_stride, int64_t o_row_stride,
                      float scale, void* stream);
 
 /* Same with q/o holding q_frames frames per batch element and k/v holding kv_frames (a frame-sharded clip: the rank's
  * own query frames against the all-gathered keys/values); q/o rows are [B*q_frames][tokens], k/v rows [B*kv_frames][tokens].
- * Domain: 1 <= q_frames, kv_frames <= FZ_TEMPORAL_MAX_FRAMES (each on its own; q_frames != kv_frames is the point of this form). */
+ * Domain: 1 <= q_frames, kv_frames <= FZ_TEMPORAL_MAX_FRAMES (each on its own; q_frames != kv_frames is the point of this form);
+ * the kernel follows max(q_frames, kv_frames): > 64 the matrix-pipe kernel, > 256 the streaming one. */
 int fz_attn_temporal_ex(const void* q, const void* k, const void* v, void* o, int batch, int q_frames, int kv_frames,
                         int tokens, int heads, int head_dim, int64_t q_row_stride, int64_t kv_row_stride,
                         int64_t o_row_stride, float scale, void* stream);

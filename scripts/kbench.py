@@ -186,6 +186,31 @@ def temporal_long_bench():
     return res
 
 
+def temporal_stream_bench():
+    """Temporal attention beyond 256 frames: F = 256 (attn_temporal_long_kernel, unchanged) against F = 288 / 384 / 512
+    (attn_temporal_stream_kernel) at the four SD-1.x levels, CFG batch 2, one process.  The yardstick of a longer clip is the
+    256-frame time x (F / 256)^2 x 1.5: three matrix products (Q K^T twice, P V) where the long kernel has two.  No gate."""
+    dev = "cuda"
+    print("temporal attention launch times, batch 2, q / k / v column slices of a packed 3C buffer; ~0.2 s of back-to-back launches per shape")
+    print("%-14s %5s %12s %14s %7s %9s" % ("(tokens, C)", "F", "us", "yardstick us", "ratio", "TFLOP/s"))
+    for (tokens, c) in [(4096, 320), (1024, 640), (256, 1280), (64, 1280)]:
+        base = None
+        for f in (256, 288, 384, 512):
+            qkv = torch.randn(2 * f, tokens, 3 * c, device=dev, dtype=torch.float16)
+            out = torch.empty(2 * f, tokens, c, dtype=torch.float16, device=dev)
+
+            def run():
+                K.attn_temporal(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], out, batch=2, clip_len=f, heads=8)
+            ms = timeit(run, iters=10, warm=3)
+            ms = timeit(run, iters=max(10, min(1000, int(200.0 / ms))), warm=0)
+            base = ms if f == 256 else base
+            yard = base * (f / 256.0) ** 2 * 1.5
+            tf = 4.0 * 2 * tokens * f * f * c / ms / 1e9   # algorithmic: Q K^T once + P V
+            print("%-14s %5d %12.1f %14s %7s %9.1f" % ((tokens, c), f, ms * 1e3, "-" if f == 256 else "%.1f" % (yard * 1e3),
+                                                      "-" if f == 256 else "%.2f" % (ms / yard), tf))
+            del qkv, out
+
+
 def norms_bench():
     dev, res, F_ = "cuda", {}, 8
     for (n, tokens, c) in [(8, 4096, 320), (16, 4096, 320), (8, 4096, 640), (8, 4096, 960), (8, 1024, 640), (8, 1024, 1920),
@@ -252,6 +277,8 @@ def main():
         return conv64_bench()
     if "--norms" in sys.argv:
         return norms_bench()
+    if "--temporal-stream" in sys.argv:
+        return temporal_stream_bench()
     if "--temporal-long" in sys.argv:
         return temporal_long_bench()
     if "--temporal" in sys.argv:
