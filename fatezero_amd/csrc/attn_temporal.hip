@@ -376,16 +376,7 @@ static int tlong_launch(const TemporalLongArgs& a0, int batch, void* stream) {
     const size_t lds = a.hg * per_head;
     if (lds > 160 * 1024 || (int64_t)a.tokens * a.ngroups > 0x7fffffff || batch > 65535) return FZ_ERR_UNSUPPORTED;
     dim3 grid((unsigned)(a.tokens * a.ngroups), batch), block(TTHREADS);
-    auto launch = [&](auto kern) -> int {
-#ifndef FZ_EMU
-        if (lds > 64 * 1024) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return FZ_ERR_LAUNCH;
-        }
-#endif
-        FZ_LAUNCH(kern, grid, block, lds, stream, a);
-        return fz_last_launch_status();
-    };
+    auto launch = [&](auto kern) -> int { return FZ_LAUNCH_LDS(kern, grid, block, lds, stream, a); };
     switch (nt) {
         case 1: return launch(attn_temporal_long_kernel<1>);
         case 2: return launch(attn_temporal_long_kernel<2>);
@@ -596,16 +587,7 @@ static int tstream_launch(const TemporalStreamArgs& a0, int batch, void* stream)
     const size_t lds = hg * per_head;
     if (lds > 160 * 1024 || (int64_t)a.tokens * a.ngroups * a.nqg > 0x7fffffff || batch > 65535) return FZ_ERR_UNSUPPORTED;
     dim3 grid((unsigned)(a.tokens * a.ngroups * a.nqg), batch), block(TTHREADS);
-    auto launch = [&](auto kern) -> int {
-#ifndef FZ_EMU
-        if (lds > 64 * 1024) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return FZ_ERR_LAUNCH;
-        }
-#endif
-        FZ_LAUNCH(kern, grid, block, lds, stream, a);
-        return fz_last_launch_status();
-    };
+    auto launch = [&](auto kern) -> int { return FZ_LAUNCH_LDS(kern, grid, block, lds, stream, a); };
     switch (hg * 8 + ct) {
         case 1 * 8 + 1: return launch(attn_temporal_stream_kernel<1, 1>);
         case 1 * 8 + 2: return launch(attn_temporal_stream_kernel<1, 2>);
@@ -662,16 +644,7 @@ extern "C" int fz_attn_temporal_ex(const void* q, const void* k, const void* v, 
     if (lds <= 160 * 1024) {  // (one token of a 32-frame clip at 1280 channels is exactly 160 KB)
         a.tok_per_block = tpb_lds;
         dim3 grid((tokens + tpb_lds - 1) / tpb_lds, batch), block(TTHREADS);
-        auto launch = [&](auto kern) -> int {
-#ifndef FZ_EMU
-            if (lds > 64 * 1024) {  // opt-in function attribute, per device (cheap: only the long clips at the wide levels get here)
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                    return FZ_ERR_LAUNCH;
-            }
-#endif
-            FZ_LAUNCH(kern, grid, block, lds, stream, a);
-            return fz_last_launch_status();
-        };
+        auto launch = [&](auto kern) -> int { return FZ_LAUNCH_LDS(kern, grid, block, lds, stream, a); };
         switch (fixed ? kv_frames : 0) {
             case 8: return launch(attn_temporal_lds_kernel<8>);
             case 16: return launch(attn_temporal_lds_kernel<16>);

@@ -32,7 +32,6 @@
 // The first halo chunk is fetched by all eight waves together with one more LDS-DMA piece carrying the tile's bias slice and time-embedding row, so the
 // first MFMA issues 1.9 us after entry and the epilogue waits for no memory but the residual rows it requested before staging.
 #include "fz_rt.h"
-#include <atomic>
 #include "../../include/fatezero_hip.h"
 
 FZ_DEVICE_GLOBAL __attribute__((aligned(16))) half_t ch_zero_page[512];  // 1 KB of zeros: the source of every lane outside the image
@@ -617,25 +616,8 @@ static int conv_halo_launch_taps(int taps, int ta, const void* x, const void* wt
         if (((pl * g.w_magic) >> 16) != pl / w) return FZ_ERR_UNSUPPORTED;
     if (taps == 4 && (g.ksplit > 1 || temb != nullptr || res != nullptr)) return FZ_ERR_UNSUPPORTED;   // the upsampler's convolution: bias only
     void (*kern)(ChArgs) = taps == 4 ? &conv_halo_kernel<4> : (ta == 2 ? &conv_halo_kernel<9, 2> : &conv_halo_kernel<9>);
-#ifndef FZ_EMU
-    static std::atomic<uint64_t> attr_set_mask[3] = {{0}, {0}, {0}};  // LDS above 64 KB is an opt-in function attribute, per device and instantiation
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
-    std::atomic<uint64_t>& mask = attr_set_mask[taps == 4 ? 1 : (ta == 2 ? 2 : 0)];
-    if (dev >= 64 || !(mask.load(std::memory_order_relaxed) >> dev & 1)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return FZ_ERR_LAUNCH;
-        if (dev < 64) mask.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-#endif
-    if (taps == 4) {
-        FZ_LAUNCH(conv_halo_kernel<4>, dim3((unsigned)nwg, 1, 4), dim3(512), lds, stream, g);
-    } else if (ta == 2) {
-        FZ_LAUNCH((conv_halo_kernel<9, 2>), dim3((unsigned)nwg, (unsigned)g.ksplit), dim3(512), lds, stream, g);
-    } else {
-        FZ_LAUNCH(conv_halo_kernel<9>, dim3((unsigned)nwg, (unsigned)g.ksplit), dim3(512), lds, stream, g);
-    }
-    return fz_last_launch_status();
+    const dim3 grid = taps == 4 ? dim3((unsigned)nwg, 1, 4) : dim3((unsigned)nwg, (unsigned)g.ksplit);
+    return FZ_LAUNCH_LDS(kern, grid, dim3(512), lds, stream, g);
 }
 
 int fz_conv_halo_launch(const void* x, const void* wt, const void* bias, const void* temb, int64_t temb_stride, int64_t temb_group, const void* res,

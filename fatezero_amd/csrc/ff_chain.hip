@@ -30,7 +30,6 @@
 // to fp16, y rounded to fp16 before the residual -- the results are BIT-IDENTICAL to fz_gemm(GEGLU) + fz_gemm_lnout (tests/kernel_cases.py
 // case_ff_chain).
 #include "fz_rt.h"
-#include <atomic>
 #include <type_traits>
 #include "../../include/fatezero_hip.h"
 
@@ -452,17 +451,5 @@ extern "C" int fz_ff_chain(const void* xn, const void* packed, const void* b2, c
     g.nchunk = inner / 32;
     g.eps = ln_eps;
     const int64_t nwg = (rows + FC_ROWS - 1) / FC_ROWS;
-#ifndef FZ_EMU
-    static std::atomic<uint64_t> attr_set_mask{0};  // LDS above 64 KB is an opt-in function attribute, per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
-    if (dev >= 64 || !(attr_set_mask.load(std::memory_order_relaxed) >> dev & 1)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)FC_LDS_BYTES) != hipSuccess)
-            return FZ_ERR_LAUNCH;
-        if (dev < 64) attr_set_mask.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-#endif
-    FZ_LAUNCH(ff_chain_kernel, dim3((unsigned)nwg), dim3(512), FC_LDS_BYTES, stream, g);
-    return fz_last_launch_status();
+    return FZ_LAUNCH_LDS(ff_chain_kernel, dim3((unsigned)nwg), dim3(512), FC_LDS_BYTES, stream, g);
 }

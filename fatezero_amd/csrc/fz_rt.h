@@ -429,6 +429,7 @@ static inline int fz_round_up(int a, int b) { return fz_ceil_div(a, b) * b; }
 // (latents, the timestep embedding, the step's map slabs, masks): fz_plan_relocate rewrites every pointer-sized argument word of a record
 // range that points into [old, old + bytes) to the same offset from `new_base`.  (csrc/plan.hip; host side: fatezero_amd/issue.py)
 #include <string.h>
+#include <atomic>
 #include <vector>
 
 namespace fz_plan {
@@ -512,4 +513,51 @@ inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t smem, voi
     FZ_RAW_LAUNCH(kernel, grid, block, smem, stream, a...);
 }
 
+// Dynamic LDS above 64 KB is an opt-in function attribute (hipFuncAttributeMaxDynamicSharedMemorySize) PER KERNEL AND DEVICE: a process
+// that drives a second GPU must set it there as well.  It is a permission, not an allocation, and what a kernel asks for may differ from
+// launch to launch (csrc/attn_temporal.hip), so it is set ONCE to the 160 KB a workgroup can have at all.  Which (kernel, device) pairs
+// have it is kept in a lock-free open-addressed table keyed on the kernel's address -- kernels reach a launch as run-time-selected
+// function pointers -- with bit d of a slot = set on device ordinal d.  Ordinals >= 64 (and a full table) set it on every launch.
+#ifndef FZ_EMU
+constexpr size_t kLdsOptInBytes = 160 * 1024;
+struct LdsOptIn {
+    std::atomic<const void*> kernel{nullptr};
+    std::atomic<uint64_t> devices{0};
+};
+inline LdsOptIn g_lds_opt_in[512];
+
+inline int lds_opt_in(const void* kernel) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
+    LdsOptIn* slot = nullptr;
+    if (dev < 64) {
+        size_t i = (size_t)(((uintptr_t)kernel >> 4) * 0x9E3779B97F4A7C15ull >> 55);
+        for (int probes = 0; probes < 512 && slot == nullptr; ++probes, i = (i + 1) & 511) {
+            const void* k = g_lds_opt_in[i].kernel.load(std::memory_order_relaxed);
+            if (k == nullptr && g_lds_opt_in[i].kernel.compare_exchange_strong(k, kernel, std::memory_order_relaxed)) k = kernel;
+            if (k == kernel) slot = &g_lds_opt_in[i];   // (a lost exchange left the winner in k: this kernel, or the probe goes on)
+        }
+        if (slot != nullptr && (slot->devices.load(std::memory_order_relaxed) >> dev & 1)) return FZ_OK;
+    }
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptInBytes) != hipSuccess) return FZ_ERR_LAUNCH;
+    if (slot != nullptr) slot->devices.fetch_or(1ull << dev, std::memory_order_relaxed);
+    return FZ_OK;
+}
+#endif
+
+// fz_plan::launch for a kernel whose dynamic LDS may exceed 64 KB; returns the launch status.  Every kernel family with opt-in LDS
+// launches through this.
+template <typename... P, typename... A>
+inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t smem, void* stream, A&&... a) {
+#ifndef FZ_EMU
+    if (smem > 64 * 1024) {
+        if (smem > kLdsOptInBytes || lds_opt_in(reinterpret_cast<const void*>(kernel)) != FZ_OK) return FZ_ERR_LAUNCH;
+    }
+#endif
+    FZ_LAUNCH(kernel, grid, block, smem, stream, a...);
+    return fz_last_launch_status();
+}
+
 }  // namespace fz_plan
+
+#define FZ_LAUNCH_LDS(kernel, grid, block, smem, stream, ...) fz_plan::launch_lds(kernel, grid, block, smem, (void*)(stream), __VA_ARGS__)

@@ -23,7 +23,6 @@
 // igemm_reduce_kernel combines with the same tail.
 #include "fz_rt.h"
 #include <type_traits>
-#include <atomic>
 #include <utility>
 #include <stdlib.h>
 #include "../../include/fatezero_hip.h"
@@ -1360,18 +1359,6 @@ static int ig_launch(IgArgs g, int batch, void* stream) {
     const int64_t nt = (int64_t)g.tiles_a * tiles_b;
     if (nt <= 0 || nt >= (1ll << 31) || batch <= 0 || batch > 65535 || g.ksplit < 1 || g.ksplit > 65535) return FZ_ERR_BAD_ARG;
     const size_t lds = (size_t)C::LDS_HALVES * sizeof(half_t);
-#ifndef FZ_EMU
-    // LDS above 64 KB is an opt-in function attribute -- PER DEVICE: a process that drives a second GPU must set it there as well
-    static std::atomic<uint64_t> attr_set_mask{0};  // bit d = set on device ordinal d (ordinals >= 64: set on every launch)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
-    if (dev >= 64 || !(attr_set_mask.load(std::memory_order_relaxed) >> dev & 1)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, PP, VT, GS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return FZ_ERR_LAUNCH;
-        if (dev < 64) attr_set_mask.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-#endif
     // Tile order.  An XCD (32 CUs, its own 4 MB L2) runs ~32 consecutive tiles of the launch order at a time and fetches what those tiles
     // span into its L2.  With the a-tile fastest that is min(tiles_a, 32) weight panels x 1-2 row panels; with groups of group_b b-tiles
     // it is a 2-D block of (32 / group_b) weight panels x group_b row panels.  The launcher prices one such round for group_b in
@@ -1425,8 +1412,7 @@ static int ig_launch(IgArgs g, int batch, void* stream) {
         static_assert((C::RP * C::CSTR + 2 * 3 * 16 * (C::CW / GS)) <= C::LDS_HALVES, "GroupNorm-statistics scratch does not fit");
         static_assert(C::RP == 128, "the partials' chunk is 128 rows whatever the tile");
     }
-    FZ_LAUNCH((igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, PP, VT, GS>), grid, block, lds, stream, g);
-    return fz_last_launch_status();
+    return FZ_LAUNCH_LDS((igemm_kernel<WA, TA, WB, TB, BK, NS, MODE, GEGLU, PP, VT, GS>), grid, block, lds, stream, g);
 }
 
 // Tile configurations.  id = WA TA WB TB (decimal digits) * 100 + (BK / 32) * 10 + NS, e.g. 254222 = 2 x 4 waves of 5 x 2 MFMA
@@ -1629,6 +1615,14 @@ static void ig_choose(const IgArgs& g, int batch, bool geglu, int64_t ws_floats,
     }
 }
 
+// the split-K tail: sums the g.ksplit fp32 slabs at g.part and applies the epilogue (one wave per row, 4 rows per workgroup)
+static int ig_reduce_launch(const IgArgs& g, int batch, void* stream) {
+    const int64_t rblocks = (g.Nb * batch + 3) / 4;
+    dim3 grid((unsigned)(rblocks < 16384 ? rblocks : 16384), (unsigned)((g.Ma / 4 + 63) / 64)), block(256);
+    FZ_LAUNCH(igemm_reduce_kernel, grid, block, 0, stream, g, batch);
+    return fz_last_launch_status();
+}
+
 template <int MODE, bool GEGLU>
 static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, int64_t workspace_floats, void* stream) {
     if (g.Cin % 8 || g.Cin > 8128 || g.Cin <= 0) return FZ_ERR_UNSUPPORTED;
@@ -1722,10 +1716,7 @@ static int ig_run(IgArgs g, int batch, int cfg, int ksplit, float* workspace, in
     }
     const int rc = ig_dispatch_cfg<MODE, GEGLU>(cfg, g, batch, stream);
     if (rc != FZ_OK || ksplit == 1) return rc != FZ_OK ? rc : (gs_dropped ? FZ_GEMM_NO_STATS : FZ_OK);
-    const int64_t rblocks = (g.Nb * batch + 3) / 4;   // one wave per row, 4 rows per workgroup
-    dim3 grid((unsigned)(rblocks < 16384 ? rblocks : 16384), (unsigned)((g.Ma / 4 + 63) / 64)), block(256);
-    FZ_LAUNCH(igemm_reduce_kernel, grid, block, 0, stream, g, batch);
-    const int rc2 = fz_last_launch_status();
+    const int rc2 = ig_reduce_launch(g, batch, stream);
     return rc2 != FZ_OK ? rc2 : (gs_dropped ? FZ_GEMM_NO_STATS : FZ_OK);
 }
 
@@ -1736,49 +1727,74 @@ extern "C" int64_t fz_gemm_workspace_floats(int64_t rows, int out_features, int 
     return 8 * out < cap ? 8 * out : (2 * out < cap ? cap : 2 * out);
 }
 
-extern "C" int fz_gemm(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2,
-                       void* y, void* workspace, void* stream) {
-    if (!d || !x || !w || !y || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
-    const int batch = d->batch > 0 ? d->batch : 1;
+// FzGemmDesc + operands -> IgArgs, ONCE for every fz_gemm* entry point.  `allow` says what the entry point takes of a descriptor:
+enum : unsigned {
+    IG_D_BATCH = 1,      // batch > 1 and the batch strides of x / w / y / the residuals
+    IG_D_TRANSPOSE = 2,  // transpose_out (V^T)
+    IG_D_GEGLU = 4,      // the GEGLU epilogue
+    IG_D_SPLITK = 8,     // split_k and the workspace
+    IG_D_RES = 16,       // residual operands: res_rows is validated
+};
+struct IgCall {  // what ig_run takes
     IgArgs g = {};
+    int batch = 1, split_k = 1;
+    float* workspace = nullptr;
+    int64_t workspace_floats = 0;
+    bool geglu = false;
+};
+// y_cols: the columns y must hold (0: what the descriptor implies -- out_features, half of it under GEGLU, the stored rows of a V^T).
+// The order of the checks is part of the ABI: what an entry point does not allow is FZ_ERR_UNSUPPORTED ahead of every FZ_ERR_BAD_ARG about
+// the sizes, and what the V^T / GEGLU forms cannot carry is FZ_ERR_UNSUPPORTED behind them (tests/test_gemm_entry_codes_emu.py).
+static int ig_from_desc(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2, void* y,
+                        void* workspace, unsigned allow, int64_t y_cols, IgCall& c) {
+    if (!d || !x || !w || !y || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
+    if ((!(allow & IG_D_GEGLU) && d->epilogue != FZ_GEMM_PLAIN) || (!(allow & IG_D_TRANSPOSE) && d->transpose_out) ||
+        (!(allow & IG_D_BATCH) && (d->batch > 1 || d->w_batch_stride)))
+        return FZ_ERR_UNSUPPORTED;
+    c.batch = d->batch > 0 ? d->batch : 1;
+    c.geglu = d->epilogue == FZ_GEMM_GEGLU;
+    if ((allow & IG_D_RES) && (d->res_rows < 0 || (d->res_rows > 0 && (c.batch != 1 || d->transpose_out || d->rows >= (1ll << 31)))))
+        return FZ_ERR_BAD_ARG;
+    if (d->ldx < d->in_features || d->ldw < d->in_features || (d->ldx % 8) || (d->ldw % 8)) return FZ_ERR_BAD_ARG;
+    if (d->epilogue != FZ_GEMM_PLAIN && !c.geglu) return FZ_ERR_BAD_ARG;
+    IgArgs& g = c.g;
     g.taps = 1;
     g.fpb = 1;
     g.Cin = d->in_features;
-    g.temb = nullptr;
     g.temb_group = 1;
     g.res = (const half_t*)res;
     g.res2 = (const half_t*)res2;
     g.ldres = d->ldres ? d->ldres : d->ldy;
-    g.res_bs = d->res_batch_stride;
-    if (d->res_rows < 0 || (d->res_rows > 0 && (batch != 1 || d->transpose_out || d->rows >= (1ll << 31)))) return FZ_ERR_BAD_ARG;
     g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
     g.y = (half_t*)y;
     g.ldy = d->ldy;
-    g.y_bs = d->y_batch_stride;
-    if (d->ldx < d->in_features || d->ldw < d->in_features || (d->ldx % 8) || (d->ldw % 8)) return FZ_ERR_BAD_ARG;
-    const bool geglu = d->epilogue == FZ_GEMM_GEGLU;
-    if (d->epilogue != FZ_GEMM_PLAIN && !geglu) return FZ_ERR_BAD_ARG;
+    if (allow & IG_D_BATCH) {
+        g.res_bs = d->res_batch_stride;
+        g.y_bs = d->y_batch_stride;
+    }
     if (!d->transpose_out) {  // y[row][out]:  A = W (out features), B = x rows
         g.a = (const half_t*)w;
         g.lda = d->ldw;
-        g.a_bs = d->w_batch_stride;  // 0: shared weights
-        g.Ma = d->out_features;
-        g.Ma_store = d->out_features;
+        g.Ma = g.Ma_store = d->out_features;
         g.b = (const half_t*)x;
         g.ldb = d->ldx;
-        g.b_bs = d->x_batch_stride;
         g.Nb = d->rows;
         g.bias = (const half_t*)bias;
-        const int outw = geglu ? d->out_features / 2 : d->out_features;
-        if (d->ldy < outw) return FZ_ERR_BAD_ARG;
-        if (geglu) {
-            if (d->out_features % 64 || res || res2) return FZ_ERR_UNSUPPORTED;
-            return ig_run<0, true>(g, batch, d->tile_cfg, 1, nullptr, 0, stream);
+        if (allow & IG_D_BATCH) {
+            g.a_bs = d->w_batch_stride;  // 0: shared weights
+            g.b_bs = d->x_batch_stride;
         }
-        return ig_run<0, false>(g, batch, d->tile_cfg, d->split_k, (float*)workspace, d->workspace_floats, stream);
+        if (d->ldy < (y_cols ? y_cols : (c.geglu ? d->out_features / 2 : d->out_features))) return FZ_ERR_BAD_ARG;
+        if (c.geglu && (d->out_features % 64 || res || res2)) return FZ_ERR_UNSUPPORTED;
+        if ((allow & IG_D_SPLITK) && !c.geglu) {
+            c.split_k = d->split_k;
+            c.workspace = (float*)workspace;
+            c.workspace_floats = d->workspace_floats;
+        }
+        return FZ_OK;
     }
     // y[b][out][row] (V^T): A = x rows of the batch element (row index contiguous in the output), B = W rows
-    if (geglu || bias || res || res2) return FZ_ERR_UNSUPPORTED;
+    if (c.geglu || bias || res || res2) return FZ_ERR_UNSUPPORTED;
     if (d->rows >= (1ll << 31)) return FZ_ERR_UNSUPPORTED;
     g.a = (const half_t*)x;
     g.lda = d->ldx;
@@ -1787,34 +1803,32 @@ extern "C" int fz_gemm(const FzGemmDesc* d, const void* x, const void* w, const 
     g.Ma_store = d->rows_store > d->rows ? (int)d->rows_store : (int)d->rows;
     g.b = (const half_t*)w;
     g.ldb = d->ldw;
-    g.b_bs = 0;
     g.Nb = d->out_features;
-    g.bias = nullptr;
-    if (d->ldy < g.Ma_store) return FZ_ERR_BAD_ARG;
-    return ig_run<0, false>(g, batch, d->tile_cfg, 1, nullptr, 0, stream);
+    return d->ldy < g.Ma_store ? FZ_ERR_BAD_ARG : FZ_OK;
+}
+static int ig_call_run(const IgCall& c, int cfg, void* stream) {
+    return c.geglu ? ig_run<0, true>(c.g, c.batch, cfg, 1, nullptr, 0, stream)
+                   : ig_run<0, false>(c.g, c.batch, cfg, c.split_k, c.workspace, c.workspace_floats, stream);
+}
+
+extern "C" int fz_gemm(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2,
+                       void* y, void* workspace, void* stream) {
+    IgCall c;
+    const int rc = ig_from_desc(d, x, w, bias, res, res2, y, workspace, IG_D_BATCH | IG_D_TRANSPOSE | IG_D_GEGLU | IG_D_SPLITK | IG_D_RES, 0, c);
+    return rc != FZ_OK ? rc : ig_call_run(c, d->tile_cfg, stream);
 }
 
 extern "C" int fz_gemm_qkvt(const FzGemmDesc* d, const void* x, const void* w, void* y, void* yt, int split_col, int64_t rows_per_frame,
                             int64_t yt_frame_stride, int64_t ldyt, void* stream) {
-    if (!d || !x || !w || !y || !yt || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
-    if (d->epilogue != FZ_GEMM_PLAIN || d->transpose_out || (d->batch > 1) || d->w_batch_stride) return FZ_ERR_UNSUPPORTED;
+    if (!yt) return FZ_ERR_BAD_ARG;
+    IgCall c;
+    const int rc = ig_from_desc(d, x, w, nullptr, nullptr, nullptr, y, nullptr, 0, split_col > 0 ? split_col : 1, c);
+    if (rc != FZ_OK) return rc;
     if (split_col <= 0 || split_col >= d->out_features || split_col % 64 || rows_per_frame <= 0 || rows_per_frame % 8 ||
-        d->rows % rows_per_frame || ldyt < rows_per_frame || (ldyt % 8) || (yt_frame_stride % 8) || d->ldy < split_col || (d->ldy % 8))
+        d->rows % rows_per_frame || ldyt < rows_per_frame || (ldyt % 8) || (yt_frame_stride % 8) || (d->ldy % 8) || d->rows >= (1ll << 31))
         return FZ_ERR_BAD_ARG;
-    if (d->ldx < d->in_features || d->ldw < d->in_features || (d->ldx % 8) || (d->ldw % 8) || d->rows >= (1ll << 31)) return FZ_ERR_BAD_ARG;
-    IgArgs g = {};
-    g.taps = 1;
-    g.fpb = 1;
-    g.Cin = d->in_features;
-    g.temb_group = 1;
-    g.a = (const half_t*)w;
-    g.lda = d->ldw;
-    g.Ma = g.Ma_store = d->out_features;
-    g.b = (const half_t*)x;
-    g.ldb = d->ldx;
-    g.Nb = d->rows;
-    g.y = (half_t*)y;
-    g.ldy = g.ldres = d->ldy;
+    IgArgs& g = c.g;
+    g.ldres = d->ldy;
     g.yt = (half_t*)yt;
     g.yt_bs = yt_frame_stride;
     g.ldyt = ldyt;
@@ -1830,7 +1844,7 @@ extern "C" int fz_gemm_qkvt(const FzGemmDesc* d, const void* x, const void* w, v
         }
         if (split_col % ba) return FZ_ERR_BAD_ARG;
     }
-    return ig_run<0, false>(g, 1, d->tile_cfg, 1, nullptr, 0, stream);
+    return ig_call_run(c, d->tile_cfg, stream);
 }
 
 static int conv_common(IgArgs& g, const void* x, const void* wt, const void* bias, const void* temb, int64_t temb_stride,
@@ -1910,64 +1924,28 @@ extern "C" int fz_gn_epilogue_chunks(int64_t rows_per_frame) { return rows_per_f
 
 extern "C" int fz_gemm_gn(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2, void* y,
                           float* gn_partial, int gn_groups, int64_t rows_per_frame, void* stream) {
-    if (!d || !x || !w || !y || !gn_partial || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
-    if (d->epilogue != FZ_GEMM_PLAIN || d->transpose_out || d->batch > 1 || d->w_batch_stride) return FZ_ERR_UNSUPPORTED;
-    if (d->ldx < d->in_features || d->ldw < d->in_features || (d->ldx % 8) || (d->ldw % 8) || d->ldy < d->out_features) return FZ_ERR_BAD_ARG;
-    IgArgs g = {};
-    g.taps = 1;
-    g.fpb = 1;
-    g.Cin = d->in_features;
-    g.temb_group = 1;
-    g.a = (const half_t*)w;
-    g.lda = d->ldw;
-    g.Ma = g.Ma_store = d->out_features;
-    g.b = (const half_t*)x;
-    g.ldb = d->ldx;
-    g.Nb = d->rows;
-    g.bias = (const half_t*)bias;
-    g.res = (const half_t*)res;
-    g.res2 = (const half_t*)res2;
-    g.y = (half_t*)y;
-    g.ldy = d->ldy;
-    g.ldres = d->ldres ? d->ldres : d->ldy;
-    if (d->res_rows < 0 || (d->res_rows > 0 && d->rows >= (1ll << 31))) return FZ_ERR_BAD_ARG;
-    g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
-    const bool want = ig_gs_setup(g, gn_partial, gn_groups, rows_per_frame);
-    const int rc = ig_run<0, false>(g, 1, d->tile_cfg, 1, nullptr, 0, stream);
+    if (!gn_partial) return FZ_ERR_BAD_ARG;
+    IgCall c;
+    const int rc0 = ig_from_desc(d, x, w, bias, res, res2, y, nullptr, IG_D_RES, 0, c);
+    if (rc0 != FZ_OK) return rc0;
+    const bool want = ig_gs_setup(c.g, gn_partial, gn_groups, rows_per_frame);
+    const int rc = ig_call_run(c, d->tile_cfg, stream);
     return rc != FZ_OK ? rc : (want ? FZ_OK : FZ_GEMM_NO_STATS);
 }
 
 extern "C" int fz_gemm_lnout(const FzGemmDesc* d, const void* x, const void* w, const void* bias, const void* res, const void* res2, void* y,
                              const void* gamma, const void* beta, float eps, void* y_ln, int64_t ld_ln, void* workspace, void* stream) {
-    if (!d || !x || !w || !y || !gamma || !beta || !y_ln || d->rows <= 0 || d->in_features <= 0 || d->out_features <= 0) return FZ_ERR_BAD_ARG;
-    if (d->epilogue != FZ_GEMM_PLAIN || d->transpose_out || d->batch > 1 || d->w_batch_stride) return FZ_ERR_UNSUPPORTED;
-    if (d->ldx < d->in_features || d->ldw < d->in_features || (d->ldx % 8) || (d->ldw % 8) || d->ldy < d->out_features || ld_ln < d->out_features)
-        return FZ_ERR_BAD_ARG;
-    IgArgs g = {};
-    g.taps = 1;
-    g.fpb = 1;
-    g.Cin = d->in_features;
-    g.temb_group = 1;
-    g.a = (const half_t*)w;
-    g.lda = d->ldw;
-    g.Ma = g.Ma_store = d->out_features;
-    g.b = (const half_t*)x;
-    g.ldb = d->ldx;
-    g.Nb = d->rows;
-    g.bias = (const half_t*)bias;
-    g.res = (const half_t*)res;
-    g.res2 = (const half_t*)res2;
-    g.y = (half_t*)y;
-    g.ldy = d->ldy;
-    g.ldres = d->ldres ? d->ldres : d->ldy;
-    if (d->res_rows < 0 || (d->res_rows > 0 && d->rows >= (1ll << 31))) return FZ_ERR_BAD_ARG;
-    g.res_rows = (res != nullptr && d->res_rows > 0 && d->res_rows < d->rows) ? d->res_rows : 0;
-    g.lno_y = (half_t*)y_ln;
-    g.lno_gamma = (const half_t*)gamma;
-    g.lno_beta = (const half_t*)beta;
-    g.lno_ld = ld_ln;
-    g.lno_eps = eps;
-    return ig_run<0, false>(g, 1, d->tile_cfg, d->split_k, (float*)workspace, d->workspace_floats, stream);
+    if (!gamma || !beta || !y_ln) return FZ_ERR_BAD_ARG;
+    IgCall c;
+    const int rc = ig_from_desc(d, x, w, bias, res, res2, y, workspace, IG_D_RES | IG_D_SPLITK, 0, c);
+    if (rc != FZ_OK) return rc;
+    if (ld_ln < d->out_features) return FZ_ERR_BAD_ARG;
+    c.g.lno_y = (half_t*)y_ln;
+    c.g.lno_gamma = (const half_t*)gamma;
+    c.g.lno_beta = (const half_t*)beta;
+    c.g.lno_ld = ld_ln;
+    c.g.lno_eps = eps;
+    return ig_call_run(c, d->tile_cfg, stream);
 }
 
 static int temporal_conv3_impl(const void* x, const void* wt, const void* res, const void* res2, const void* temb, int64_t temb_stride,
@@ -2029,10 +2007,7 @@ static int conv_halo_run(IgArgs& g, const void* x, const void* wt, const void* b
     if (rc != FZ_OK) return rc;
     g.ksplit = ksplit;
     g.part = workspace;
-    const int64_t rblocks = (g.Nb + 3) / 4;
-    dim3 grid((unsigned)(rblocks < 16384 ? rblocks : 16384), (unsigned)((g.Ma / 4 + 63) / 64)), block(256);
-    FZ_LAUNCH(igemm_reduce_kernel, grid, block, 0, stream, g, 1);
-    return fz_last_launch_status();
+    return ig_reduce_launch(g, 1, stream);
 }
 #define FZ_TILE_CONV_HALO 154299
 #define FZ_TILE_CONV_HALO64 154264   /* the same kernel with 64 output channels per workgroup (conv_halo_kernel<9, 2>) */

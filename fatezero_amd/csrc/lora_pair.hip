@@ -364,26 +364,7 @@ static int lora_pair_launch(const void* x, const void* w_down, const void* w_up,
     if (blocks <= 0 || blocks >= (1ll << 31)) return FZ_ERR_BAD_ARG;
     const size_t lds = (size_t)LP_LDS_HALVES * sizeof(half_t);
     void (*kern)(LoraPairArgs) = gs == 10 ? &lora_pair_kernel<10> : (gs == 20 ? &lora_pair_kernel<20> : &lora_pair_kernel<0>);
-#ifndef FZ_EMU
-    static unsigned long long attr_mask[3] = {0, 0, 0};
-    const int ki = gs == 10 ? 1 : (gs == 20 ? 2 : 0);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
-    if (dev >= 64 || !((attr_mask[ki] >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return FZ_ERR_LAUNCH;
-        if (dev < 64) attr_mask[ki] |= 1ull << dev;
-    }
-#endif
-    if (gs == 10) {
-        FZ_LAUNCH(lora_pair_kernel<10>, dim3((unsigned)blocks), dim3(512), lds, stream, g);
-    } else if (gs == 20) {
-        FZ_LAUNCH(lora_pair_kernel<20>, dim3((unsigned)blocks), dim3(512), lds, stream, g);
-    } else {
-        FZ_LAUNCH(lora_pair_kernel<0>, dim3((unsigned)blocks), dim3(512), lds, stream, g);
-    }
-    (void)kern;
-    return fz_last_launch_status();
+    return FZ_LAUNCH_LDS(kern, dim3((unsigned)blocks), dim3(512), lds, stream, g);
 }
 
 extern "C" int fz_lora_pair(const void* x, const void* w_down, const void* w_up, const void* temb, int64_t temb_stride, const void* res2,

@@ -31,7 +31,6 @@
 // scores scaled in fp32, max / sum / exp2 / reciprocal in attn_cross.hip's order, every intermediate rounded to fp16 where the launches
 // store it -- the results are BIT-IDENTICAL to fz_gemm + fz_attn_cross + fz_gemm_lnout (tests/kernel_cases.py case_xattn_chain).
 #include "fz_rt.h"
-#include <atomic>
 #include <type_traits>
 #include "../../include/fatezero_hip.h"
 
@@ -828,20 +827,6 @@ extern "C" int fz_xattn_chain(const FzXattnChain* d, void* stream) {
     g.eps = d->ln_eps;
     g.eps1 = d->ln1_eps;
     const int64_t nwg = d->rows / XC_ROWS;
-#ifndef FZ_EMU
-    static std::atomic<uint64_t> attr_set_mask[2] = {{0}, {0}};  // LDS above 64 KB is an opt-in function attribute, per device and kernel
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FZ_ERR_LAUNCH;
-    if (dev >= 64 || !(attr_set_mask[front].load(std::memory_order_relaxed) >> dev & 1)) {
-        const void* fn = front ? reinterpret_cast<const void*>(&xattn_chain_kernel<true>) : reinterpret_cast<const void*>(&xattn_chain_kernel<false>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)XC_LDS_BYTES) != hipSuccess) return FZ_ERR_LAUNCH;
-        if (dev < 64) attr_set_mask[front].fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
-#endif
-    if (front) {
-        FZ_LAUNCH(xattn_chain_kernel<true>, dim3((unsigned)nwg), dim3(512), XC_LDS_BYTES, stream, g);
-    } else {
-        FZ_LAUNCH(xattn_chain_kernel<false>, dim3((unsigned)nwg), dim3(512), XC_LDS_BYTES, stream, g);
-    }
-    return fz_last_launch_status();
+    void (*kern)(XcArgs) = front ? &xattn_chain_kernel<true> : &xattn_chain_kernel<false>;
+    return FZ_LAUNCH_LDS(kern, dim3((unsigned)nwg), dim3(512), XC_LDS_BYTES, stream, g);
 }

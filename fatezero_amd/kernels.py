@@ -25,11 +25,6 @@ def _raw_stream(dev_index: int) -> int:
     return torch._C._cuda_getCurrentRawStream(dev_index)
 
 
-def refresh_stream():
-    """Kept for callers of earlier revisions: the launch stream is read from PyTorch at EVERY launch now (per device), so there is
-    nothing to refresh."""
-
-
 _launches = [0]
 
 
@@ -301,6 +296,20 @@ def scratch_buffers(t_or_device):
     return [b for b in (_ws.get(key), _gn_scratch.get(key)) if b is not None]
 
 
+def _gn_scratch_buf(x: torch.Tensor, n: int, tokens: int, c: int, span: int, groups: int) -> torch.Tensor:
+    """The GroupNorm scratch of x's (device, stream), large enough for n frames of [tokens, c]: the per-chunk Welford partials and the
+    merged statistics.  (Re)allocated on need -- the cached launch plans hold its pointer and are dropped with it."""
+    need = n * N.lib().fz_groupnorm_chunks(tokens, c) * groups * 3 + (n // span) * groups * 2
+    skey = _scratch_key(x)
+    buf = _gn_scratch.get(skey)
+    if buf is None or buf.numel() < need:
+        buf = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=x.device)
+        _gn_scratch[skey] = buf
+        _gn_plans.clear()  # plans hold the scratch pointer
+        _scratch_gen[0] += 1
+    return buf
+
+
 def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, span: int, groups: int, eps: float,
               silu: bool, out: Optional[torch.Tensor] = None):
     """x: [N, tokens, C] contiguous fp16; statistics shared by `span` consecutive frames."""
@@ -310,15 +319,7 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, span:
         n, tokens, c = x.shape
         assert x.is_contiguous()
         _chk16(x, gamma, beta)
-        chunks = N.lib().fz_groupnorm_chunks(tokens, c)
-        need = n * chunks * groups * 3 + (n // span) * groups * 2
-        skey = _scratch_key(x)
-        buf = _gn_scratch.get(skey)
-        if buf is None or buf.numel() < need:
-            buf = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=x.device)
-            _gn_scratch[skey] = buf
-            _gn_plans.clear()  # plans hold the scratch pointer
-            _scratch_gen[0] += 1
+        buf = _gn_scratch_buf(x, n, tokens, c, span, groups)
         plan = _gn_plans[key] = (n, tokens, c, buf.data_ptr(), buf)
     n, tokens, c, scratch, _ = plan
     # cheap per-call checks (the plan is keyed on the shape only: a later non-contiguous / non-fp16 / misaligned tensor of the same
@@ -350,15 +351,7 @@ def groupnorm_cat(x1: torch.Tensor, x2: torch.Tensor, gamma: torch.Tensor, beta:
         raise ValueError("fz_groupnorm_cat: two contiguous fp16 tensors [N, tokens, C1] / [N, tokens, C2], gamma / beta over C1 + C2")
     _chk16(x1, x2, gamma, beta)
     c = c1 + c2
-    chunks = N.lib().fz_groupnorm_chunks(tokens, c)
-    need = n * chunks * groups * 3 + (n // span) * groups * 2
-    skey = _scratch_key(x1)
-    buf = _gn_scratch.get(skey)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty(max(need, 1 << 20), dtype=torch.float32, device=x1.device)
-        _gn_scratch[skey] = buf
-        _gn_plans.clear()  # plans hold the scratch pointer
-        _scratch_gen[0] += 1
+    buf = _gn_scratch_buf(x1, n, tokens, c, span, groups)
     out = torch.empty(n, tokens, c, dtype=torch.float16, device=x1.device)
     N.check(N.lib().fz_groupnorm_cat(x1.data_ptr(), c1, x2.data_ptr(), c2, out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n, span,
                                      tokens, groups, eps, 1 if silu else 0, buf.data_ptr(), n2 if n2 < n else 0, _stream(x1)), "fz_groupnorm_cat")
@@ -424,10 +417,7 @@ def gemm_gn(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, r
     res_rows = _res_rows(res, rows, o)
     if res is not None and (not res.is_contiguous() or (res.shape != y.shape and not res_rows)):
         return _gemm_unwrapped(x, w, bias, res=res), None
-    d = N.FzGemmDesc()
-    d.rows, d.in_features, d.out_features = rows, k, o
-    d.ldx, d.ldw, d.ldy, d.ldres = k, w.stride(0), o, o
-    d.batch, d.epilogue, d.res_rows, d.tile_cfg = 1, N.FZ_GEMM_PLAIN, res_rows, tile_cfg
+    d = _gemm_desc(rows, k, o, k, w.stride(0), o, ldres=o, res_rows=res_rows, tile_cfg=tile_cfg)
     partial = torch.empty(rows // rows_per_frame, gn_groups, rows_per_frame // 128, 3, dtype=torch.float32, device=x.device)
     rc = N.lib().fz_gemm_gn(C.byref(d), x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
                             None if res is None else res.data_ptr(), None, y.data_ptr(), partial.data_ptr(), gn_groups, rows_per_frame,
@@ -450,6 +440,27 @@ def _res_rows(res: Optional[torch.Tensor], rows: int, ow: int) -> int:
     if rr <= 0 or rows % rr or res.numel() != rr * ow:
         raise ValueError(f"fz_gemm: a residual of {rr} rows cannot be broadcast over {rows} output rows")
     return rr
+
+
+def _gemm_desc(rows: int, k: int, o: int, ldx: int, ldw: int, ldy: int, *, ldres: int = 0, batch: int = 1, batch_strides=(0, 0, 0),
+               geglu: bool = False, tile_cfg: int = 0, split_k: int = 0, res_rows: int = 0, rows_store: int = 0, transpose_out: bool = False,
+               workspace: bool = False):
+    """The FzGemmDesc of a launch (include/fatezero_hip.h); batch_strides = (x, w, y).  Every wrapper over fz_gemm* builds its descriptor
+    here; `workspace`: the launch is handed the split-K scratch (_ws_ok)."""
+    d = N.FzGemmDesc()
+    d.rows, d.rows_store, d.in_features, d.out_features = rows, rows_store, k, o
+    d.ldx, d.ldw, d.ldy, d.ldres = ldx, ldw, ldy, ldres
+    d.batch, d.epilogue = batch, (N.FZ_GEMM_GEGLU if geglu else N.FZ_GEMM_PLAIN)
+    d.x_batch_stride, d.w_batch_stride, d.y_batch_stride = batch_strides
+    d.transpose_out, d.tile_cfg, d.split_k, d.res_rows = int(transpose_out), tile_cfg, split_k, res_rows
+    d.workspace_floats = _WS_FLOATS if workspace else 0
+    return d
+
+
+def _ws_ok(out_rows: int, o: int, ok: bool = True) -> bool:
+    """May this launch take the split-K scratch?  Only where it can pay and the tail kernel can run: `ok` (the caller's own condition,
+    e.g. a long K), an output width that is a multiple of 4, and few enough outputs that two fp32 slabs of them fit the scratch."""
+    return bool(ok) and o % 4 == 0 and 2 * out_rows * o <= _WS_FLOATS
 
 
 def pack_conv3x3_weight(w: torch.Tensor) -> torch.Tensor:
@@ -562,14 +573,9 @@ def gemm_lnout(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], l
     _chk16(x, w, bias, res, res2, gam, bet)
     y = torch.empty(tuple(x.shape[:-1]) + (o,), dtype=torch.float16, device=x.device)
     yln = torch.empty_like(y)
-    d = N.FzGemmDesc()
-    d.rows, d.in_features, d.out_features = rows, k, o
-    d.ldx, d.ldw, d.ldy, d.ldres = k, w.stride(0), o, o
-    d.batch, d.epilogue, d.tile_cfg, d.split_k = 1, N.FZ_GEMM_PLAIN, tile_cfg, split_k
-    d.res_rows = _res_rows(res, rows, o)
-    want_ws = o % 4 == 0 and (k >= 1024 or split_k > 1) and 2 * rows * o <= _WS_FLOATS
-    if want_ws:
-        d.workspace_floats = _WS_FLOATS
+    want_ws = _ws_ok(rows, o, k >= 1024 or split_k > 1)
+    d = _gemm_desc(rows, k, o, k, w.stride(0), o, ldres=o, res_rows=_res_rows(res, rows, o), tile_cfg=tile_cfg, split_k=split_k,
+                   workspace=want_ws)
     rc = N.lib().fz_gemm_lnout(C.byref(d), x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(res), _ptr(res2), y.data_ptr(), gam.data_ptr(),
                                bet.data_ptr(), float(eps), yln.data_ptr(), o, _ws_ptr(x.device) if want_ws else None, _stream(x))
     if rc == N.FZ_GEMM_NO_STATS:
@@ -595,13 +601,9 @@ def gemm_batched(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] =
     for t in (x, w, out):
         if (t.data_ptr() & 15) or (t.stride(0) % 8) or (t.stride(1) % 8):
             raise ValueError("fz_gemm (batched): 16-byte aligned operands, row / batch strides multiples of 8 halves")
-    d = N.FzGemmDesc()
-    d.rows, d.in_features, d.out_features = rows, k, o
-    d.ldx, d.ldw, d.ldy = x.stride(1), w.stride(1), out.stride(1)
-    d.batch, d.epilogue = b, N.FZ_GEMM_PLAIN
-    d.x_batch_stride, d.w_batch_stride, d.y_batch_stride = x.stride(0), w.stride(0), out.stride(0)
-    want_ws = o % 4 == 0 and 2 * b * rows * o <= _WS_FLOATS
-    d.workspace_floats = _WS_FLOATS if want_ws else 0
+    want_ws = _ws_ok(b * rows, o)
+    d = _gemm_desc(rows, k, o, x.stride(1), w.stride(1), out.stride(1), batch=b, batch_strides=(x.stride(0), w.stride(0), out.stride(0)),
+                   workspace=want_ws)
     rc = N.lib().fz_gemm(C.byref(d), x.data_ptr(), w.data_ptr(), None, None, None, out.data_ptr(),
                          _ws_ptr(x.device) if want_ws else None, _stream(x))
     if rc:
@@ -624,24 +626,19 @@ def _gemm_plan(x, w, bias, res, res2, out, geglu, tile_cfg, split_k):
     if out is not None:
         assert out.stride(-1) == 1 and out.shape[-1] == ow and out.numel() // ow == rows and out.dtype == torch.float16
         ldy = out.stride(-2) if out.dim() > 1 else ow
-    d = N.FzGemmDesc()
-    d.rows, d.in_features, d.out_features = rows, k, o
-    d.ldx, d.ldw, d.ldy = ldx, w.stride(0), ldy
-    d.batch, d.epilogue = 1, (N.FZ_GEMM_GEGLU if geglu else N.FZ_GEMM_PLAIN)
-    d.tile_cfg, d.split_k = tile_cfg, split_k
-    d.res_rows = _res_rows(res, rows, ow)
+    res_rows = _res_rows(res, rows, ow)
     for r in (res, res2):
         if r is not None:
             assert r.shape[-1] == ow and r.stride(-1) == 1 and r.dtype == torch.float16
-            assert r.numel() // ow == rows or (r is res and d.res_rows and r.is_contiguous())
+            assert r.numel() // ow == rows or (r is res and res_rows and r.is_contiguous())
+    ldres = 0
     if res is not None:
-        d.ldres = res.stride(-2) if res.dim() > 1 else ow
+        ldres = res.stride(-2) if res.dim() > 1 else ow
         if res2 is not None:
-            assert (res2.stride(-2) if res2.dim() > 1 else ow) == d.ldres
-    # split-K scratch only where it can pay: long K and few enough outputs that the fp32 slabs stay small
-    want_ws = (not geglu) and o % 4 == 0 and (k >= 1024 or split_k > 1) and 2 * rows * o <= _WS_FLOATS
-    if want_ws:
-        d.workspace_floats = _WS_FLOATS
+            assert (res2.stride(-2) if res2.dim() > 1 else ow) == ldres
+    want_ws = _ws_ok(rows, o, not geglu and (k >= 1024 or split_k > 1))  # only where it can pay: a long K
+    d = _gemm_desc(rows, k, o, ldx, w.stride(0), ldy, ldres=ldres, geglu=geglu, tile_cfg=tile_cfg, split_k=split_k, res_rows=res_rows,
+                   workspace=want_ws)
     return (C.byref(d), out_shape, want_ws, d)
 
 
@@ -659,11 +656,8 @@ def gemm_vt(x: torch.Tensor, w: torch.Tensor, lp: int, out: Optional[torch.Tenso
     if plan is None:
         assert x.stride(2) == 1 and w.stride(1) == 1 and lp >= l and lp % 8 == 0
         _chk16(x, w, out)
-        d = N.FzGemmDesc()
-        d.rows, d.rows_store, d.in_features, d.out_features = l, lp, k, c
-        d.ldx, d.ldw, d.ldy = x.stride(1), w.stride(0), out.stride(1)
-        d.batch, d.x_batch_stride, d.y_batch_stride = n, x.stride(0), out.stride(0)
-        d.transpose_out, d.tile_cfg = 1, tile_cfg
+        d = _gemm_desc(l, k, c, x.stride(1), w.stride(0), out.stride(1), rows_store=lp, batch=n, batch_strides=(x.stride(0), 0, out.stride(0)),
+                       transpose_out=True, tile_cfg=tile_cfg)
         plan = _vt_plans[key] = (C.byref(d), d)
     rc = N.lib().fz_gemm(plan[0], x.data_ptr(), w.data_ptr(), None, None, None, out.data_ptr(), None, _stream(x))
     if rc:
@@ -859,10 +853,7 @@ def gemm_qkvt(x: torch.Tensor, w: torch.Tensor, split: int, tile_cfg: int = 0):
     if plan is None:
         if not gemm_qkvt_ok(x, w, split) or x.stride(2) != 1 or w.stride(1) != 1 or w.shape[1] != k or x.stride(0) != l * x.stride(1):
             raise ValueError("fz_gemm_qkvt: x [N, L, K] with L % 64 == 0 and a single row stride, w [split + Cv, K], split % 64 == 0")
-        d = N.FzGemmDesc()
-        d.rows, d.in_features, d.out_features = n * l, k, o
-        d.ldx, d.ldw, d.ldy = x.stride(1), w.stride(0), split
-        d.batch, d.epilogue, d.tile_cfg = 1, N.FZ_GEMM_PLAIN, tile_cfg
+        d = _gemm_desc(n * l, k, o, x.stride(1), w.stride(0), split, tile_cfg=tile_cfg)
         plan = _qkvt_plans[key] = (C.byref(d), d)
     if x.dtype != torch.float16 or w.dtype != torch.float16 or ((x.data_ptr() | w.data_ptr()) & 15):
         raise ValueError("fz_gemm_qkvt operands must be fp16 and 16-byte aligned")
@@ -893,7 +884,7 @@ def conv3x3(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor], *, 
     if temb is not None:
         assert temb.shape == (n // frames_per_batch, cout) and temb.stride(1) == 1
         ts = temb.stride(0)
-    use_ws = cout % 4 == 0 and cin % 8 == 0 and 2 * n * ho * wo * cout <= _WS_FLOATS
+    use_ws = _ws_ok(n * ho * wo, cout, cin % 8 == 0)
     rc = N.lib().fz_conv3x3(x.data_ptr(), wt.data_ptr(), None if bias is None else bias.data_ptr(),
                             None if temb is None else temb.data_ptr(), ts, None if res is None else res.data_ptr(),
                             out.data_ptr(), n, h, w, cin, cout, stride, 1 if upsample else 0, frames_per_batch,
@@ -966,7 +957,7 @@ def temporal_conv3(x: torch.Tensor, wt: torch.Tensor, *, clip_len: int, res: Opt
     if temb is not None:
         assert temb.shape == (n // clip_len, cout) and temb.stride(1) == 1 and temb.dtype == torch.float16
         ts = temb.stride(0)
-    use_ws = cout % 4 == 0 and 2 * n * tokens * cout <= _WS_FLOATS
+    use_ws = _ws_ok(n * tokens, cout)
     if gn_groups > 0:
         partial = None
         if gn_epilogue_ok(tokens, cout, gn_groups):

@@ -245,8 +245,6 @@ class UNetPseudo3DConditionModel(nn.Module):
 
     def forward_tokens(self, x: Tokens, timestep, ctx) -> Tokens:
         """x: latents as tokens [B*F, H*W, 4] fp16; ctx [B, 77, D] fp16 -> predicted noise, same layout."""
-        from ... import kernels as K
-        K.refresh_stream()
         if x.rep > 1 and not cfg_shared_head_active():
             x = x.expanded()
         temb_act = self.time_embed(timestep, x.b, x.data.device)

@@ -15,7 +15,7 @@ class Stub:
     def __init__(self):
         libc = C.CDLL(None)
         for name, (res, args) in N._SIGS.items():
-            if name in ("fz_groupnorm_chunks", "fz_gemm_workspace_floats", "fz_version"):
+            if name.endswith(("_ok", "_preferred", "_bytes", "_halves", "_chunks", "_floats", "_version")):  # pure queries: answered for real
                 setattr(self, name, getattr(real, name))
                 continue
             fn = C.CFUNCTYPE(res, *args)(("getpid", libc))  # cheap C function, ignores its arguments
