@@ -92,7 +92,7 @@ def load_config(path: str) -> Config:
     return cfg
 
 
-MAP_DTYPES = ("fp16", "e5m2")
+MAP_DTYPES = ("fp16", "e5m2", "ue4m4")
 
 
 def map_dtype_of(editing_config: Optional[Dict[str, Any]], override: Optional[str] = None) -> str:

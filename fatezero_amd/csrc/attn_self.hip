@@ -29,6 +29,13 @@
 #endif
 #define PSTR 72 /* halves; 144 B = 9 x 16 B (odd) */
 #define PSTR8 80 /* BYTES per row of the 8-bit staging tile: 64 + 16 = 5 x 16 B (odd) */
+#define PSTR8U 128 /* BYTES per row of the paired (two key tiles) 8-bit staging tile: unpadded, 16-byte chunks swizzled (fz_p8u_off) */
+// Store path of FZ_ATTN_CAPTURE8U the library instantiates: 1 = two key tiles of a kv slot leave together as 128-byte row segments,
+// 0 = every tile leaves as 64-byte segments (the store path of FZ_ATTN_CAPTURE8).  ABL bit 8 selects the OTHER form (timing tools).
+// 0 ships: on MI355X the paired form was 1 - 6 % SLOWER at the 32^2-level shape (profiles/map8u_capture_store_ab.txt).
+#ifndef FZ_CAP8U_PAIRED
+#define FZ_CAP8U_PAIRED 0
+#endif
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -45,6 +52,22 @@ FZ_DEVICE uint32_t fz_e5m2x4(uint32_t w0, uint32_t w1) {
 // the exact way back: each stored byte becomes the high byte of a half.  w = bytes e0..e3 -> lo = halves (e0, e1), hi = (e2, e3)
 FZ_DEVICE uint32_t fz_e5m2_lo_h2(uint32_t w) { return ((w << 8) & 0xFF00u) | ((w << 16) & 0xFF000000u); }
 FZ_DEVICE uint32_t fz_e5m2_hi_h2(uint32_t w) { return ((w >> 8) & 0xFF00u) | (w & 0xFF000000u); }
+// ---- UE4M4 storage of the map (FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U) --------------------------------------------------------
+// A probability's fp16 bit pattern is <= 0x3C00: sign and top exponent bit are always 0.  The stored byte is bits 13..6 of the half
+// (4 exponent bits, 4 mantissa bits, unsigned), rounded to nearest-even on the bit pattern: add 0x1F plus the bit that will become
+// the last kept one, keep bits 13..6.  The largest byte is 0xF0 (= 1.0); a carry never leaves its 16-bit half.
+FZ_DEVICE uint32_t fz_ue4m4x4(uint32_t w0, uint32_t w1) {
+    const uint32_t r0 = w0 + 0x001F001Fu + ((w0 >> 6) & 0x00010001u);
+    const uint32_t r1 = w1 + 0x001F001Fu + ((w1 >> 6) & 0x00010001u);
+    return ((r0 >> 6) & 0xFFu) | ((r0 >> 14) & 0xFF00u) | ((r1 << 10) & 0xFF0000u) | ((r1 << 2) & 0xFF000000u);
+}
+// the exact way back: byte b stands for the half b << 6.  w = bytes e0..e3 -> lo = halves (e0, e1), hi = (e2, e3)
+FZ_DEVICE uint32_t fz_ue4m4_lo_h2(uint32_t w) { return ((w << 6) & 0x3FC0u) | ((w << 14) & 0x3FC00000u); }
+FZ_DEVICE uint32_t fz_ue4m4_hi_h2(uint32_t w) { return ((w >> 10) & 0x3FC0u) | ((w >> 2) & 0x3FC00000u); }
+// Paired staging tile: 32 rows x 8 chunks of 16 B at a row stride of 128 B, chunk c of row r kept at chunk c ^ (r & 7).  Eight
+// consecutive rows at one chunk index (the writes: a lane per row) and the eight chunks of one row (the 128-byte flush) both cover
+// all 128 B of bank space.  A padded stride (144 B) would do the same but its 2 KB more per block cost D = 64 a workgroup per CU.
+FZ_DEVICE int fz_p8u_off(int row, int chunk) { return row * PSTR8U + ((chunk ^ (row & 7)) << 4); }
 FZ_DEVICE u32x4 fz_ld_b16(const uint8_t* p) { return *reinterpret_cast<const u32x4*>(p); }
 FZ_DEVICE void fz_st_b16(uint8_t* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
 FZ_DEVICE void fz_st_b16_nt(uint8_t* p, u32x4 v) {
@@ -55,7 +78,7 @@ FZ_DEVICE void fz_st_b16_nt(uint8_t* p, u32x4 v) {
 #endif
 }
 
-template <int D, int MODE>
+template <int D, int MODE, bool PAIR = false>
 struct SelfCfg {
     static_assert(D % 8 == 0, "head dim in 16-byte chunks");
     static constexpr int DP16 = (D + 15) / 16 * 16;
@@ -73,7 +96,12 @@ struct SelfCfg {
     // CAPTURE: a wave-private 32 x 64 staging tile turns the lanes' 16-byte pieces of 32 different rows into full 128-byte
     // row segments before they leave for HBM (a 16-byte write per lane is a 16-byte L2 request: 17 M requests per 268 MB map)
     // (CAPTURE8: the same tile in bytes, 32 x 64 B at a row stride of PSTR8 bytes -> full 64-byte row segments)
-    static constexpr int PS = (MODE == FZ_ATTN_CAPTURE) ? 4 * 32 * PSTR : (MODE == FZ_ATTN_CAPTURE8) ? 4 * 32 * PSTR8 / 2 : 0;
+    // (CAPTURE8U, paired store: 32 x 128 B, swizzled -> two key tiles leave as full 128-byte row segments)
+    static constexpr int PB = PAIR ? PSTR8U : PSTR8;  // bytes per row of the 8-bit staging tile
+    static constexpr int PS = (MODE == FZ_ATTN_CAPTURE)    ? 4 * 32 * PSTR
+                              : (MODE == FZ_ATTN_CAPTURE8) ? 4 * 32 * PSTR8 / 2
+                              : (MODE == FZ_ATTN_CAPTURE8U) ? 4 * 32 * PB / 2
+                                                            : 0;
     static constexpr int MAIN = 2 * STAGE + PS;
     static constexpr int LDS_HALVES = MAIN > OS ? MAIN : OS;
     static constexpr int KLD = (KVBLK * DCH + 255) / 256;  // 16-byte K chunks per thread per tile
@@ -92,16 +120,19 @@ FZ_DEVICE int fz_krow_of_key(int kk) {
     return 32 * sub + (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 
-// ABL: timing ablations of scripts/self_ab.hip only (1: no pass 1, 2: no map stores, 4: no P.V); the library instantiates 0
+// ABL: timing ablations of scripts/self_ab.hip only (1: no pass 1, 2: no map stores, 4: no P.V; 8: CAPTURE8U with the store path the
+// library does NOT ship, see FZ_CAP8U_PAIRED); the library instantiates 0
 template <int D, int MODE, int ABL = 0>
 FZ_KERNEL void __launch_bounds__(256, (D <= 80 ? 2 : 1))  // two workgroups per SIMD set wherever the registers allow it
 attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* __restrict__ k,
                  const half_t* __restrict__ vt, half_t* __restrict__ o, half_t* __restrict__ p,
                  const float* __restrict__ row_mask) {
-    typedef SelfCfg<D, MODE> C;
-    constexpr bool CAP = MODE == FZ_ATTN_CAPTURE || MODE == FZ_ATTN_CAPTURE8;
-    constexpr bool INJ = MODE == FZ_ATTN_INJECT || MODE == FZ_ATTN_INJECT8;
-    constexpr bool P8 = MODE == FZ_ATTN_CAPTURE8 || MODE == FZ_ATTN_INJECT8;  // `p` holds E5M2 bytes, its strides count bytes
+    constexpr bool U8 = MODE == FZ_ATTN_CAPTURE8U || MODE == FZ_ATTN_INJECT8U;  // `p` holds UE4M4 bytes
+    constexpr bool PAIR = MODE == FZ_ATTN_CAPTURE8U && ((FZ_CAP8U_PAIRED != 0) != ((ABL & 8) != 0));
+    typedef SelfCfg<D, MODE, PAIR> C;
+    constexpr bool CAP = MODE == FZ_ATTN_CAPTURE || MODE == FZ_ATTN_CAPTURE8 || MODE == FZ_ATTN_CAPTURE8U;
+    constexpr bool INJ = MODE == FZ_ATTN_INJECT || MODE == FZ_ATTN_INJECT8 || MODE == FZ_ATTN_INJECT8U;
+    constexpr bool P8 = MODE == FZ_ATTN_CAPTURE8 || MODE == FZ_ATTN_INJECT8 || U8;  // `p` holds bytes, its strides count bytes
     FZ_SHARED __attribute__((aligned(16))) half_t smem[C::LDS_HALVES];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lq_ = lane & 31, hi = lane >> 5;
@@ -303,7 +334,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     // ---- main pass --------------------------------------------------------------------------------------
     const bool need_k = !INJ || any_cur;
     half8_t pst[4];  // INJECT: the stored segment of the NEXT tile, in flight during the current one
-    u32x4 pst8[2];   // INJECT8: the same 32 keys as 32 bytes
+    u32x4 pst8[2];   // INJECT8 / INJECT8U: the same 32 keys as 32 bytes
     auto fetch_p = [&](int kt) {
         const int j = kt / tps, r0 = (kt % tps) * KVBLK;
         const half_t* sp = prow + (int64_t)j * d.lkf + r0;
@@ -351,7 +382,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     };
     fetch(0, need_k, true);
     if (MODE == FZ_ATTN_INJECT) fetch_p(0);
-    if (MODE == FZ_ATTN_INJECT8) fetch_p8(0);
+    if (INJ && P8) fetch_p8(0);
     stash(0, need_k, true);
     __syncthreads();
     for (int kt = 0; kt < ntiles; ++kt) {
@@ -365,11 +396,12 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                 if (p_vec && r0 + KVBLK > d.lkf && r0 + 32 * hi + 8 * c >= d.lkf) pf[c] = fz_zero_h8();
             }
         }
-        if (MODE == FZ_ATTN_INJECT8) {
+        if (INJ && P8) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {  // bytes -> halves: each stored byte is the high byte of its half (exact)
+            for (int c = 0; c < 4; ++c) {  // bytes -> halves: each stored byte is the high byte of its half (UE4M4: bits 13..6), exact
                 const uint32_t b0 = pst8[c >> 1][2 * (c & 1)], b1 = pst8[c >> 1][2 * (c & 1) + 1];
-                const u32x4 w = {fz_e5m2_lo_h2(b0), fz_e5m2_hi_h2(b0), fz_e5m2_lo_h2(b1), fz_e5m2_hi_h2(b1)};
+                const u32x4 w = U8 ? u32x4{fz_ue4m4_lo_h2(b0), fz_ue4m4_hi_h2(b0), fz_ue4m4_lo_h2(b1), fz_ue4m4_hi_h2(b1)}
+                                   : u32x4{fz_e5m2_lo_h2(b0), fz_e5m2_hi_h2(b0), fz_e5m2_lo_h2(b1), fz_e5m2_hi_h2(b1)};
                 pf[c] = __builtin_bit_cast(half8_t, w);
                 if (p_vec && r0 + KVBLK > d.lkf && r0 + 32 * hi + 8 * c >= d.lkf) pf[c] = fz_zero_h8();
             }
@@ -377,7 +409,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
         if (kt + 1 < ntiles) {
             fetch(kt + 1, need_k, true);
             if (MODE == FZ_ATTN_INJECT) fetch_p(kt + 1);
-            if (MODE == FZ_ATTN_INJECT8) fetch_p8(kt + 1);
+            if (INJ && P8) fetch_p8(kt + 1);
         }
         float alpha = 1.0f;
         if (need_k) {
@@ -452,6 +484,29 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                     if (r0 + 32 * hi + i < d.lkf) dp[i] = (uint8_t)(qb[i >> 4][(i >> 2) & 3] >> (8 * (i & 3)));
             }
         }
+        if (MODE == FZ_ATTN_CAPTURE8U && !(ABL & 2)) {
+            // as CAPTURE8: only the stored copy is rounded.  Paired store: the tile's 64 bytes go to the half of the 128-byte staging
+            // row its parity inside the kv slot names
+            u32x4 qb[2];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const u32x4 w = __builtin_bit_cast(u32x4, pf[c]);
+                qb[c >> 1][2 * (c & 1)] = fz_ue4m4x4(w[0], w[1]);
+                qb[c >> 1][2 * (c & 1) + 1] = fz_ue4m4x4(w[2], w[3]);
+            }
+            if (p_vec) {
+                uint8_t* Pw = reinterpret_cast<uint8_t*>(smem + 2 * C::STAGE) + wave * 32 * C::PB;
+                const int side = 4 * ((kt % tps) & 1);  // in 16-byte chunks
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    fz_st_b16(Pw + (PAIR ? fz_p8u_off(lq_, side + 2 * hi + c) : lq_ * C::PB + 32 * hi + 16 * c), qb[c]);
+            } else if (qvalid) {
+                uint8_t* dp = prow8 + (int64_t)j * d.lkf + r0;
+#pragma unroll
+                for (int i = 0; i < 32; ++i)
+                    if (r0 + 32 * hi + i < d.lkf) dp[i] = (uint8_t)(qb[i >> 4][(i >> 2) & 3] >> (8 * (i & 3)));
+            }
+        }
         if (INJ && any_cur) {
 #pragma unroll
             for (int t = 0; t < C::NT; ++t) oacc[t] *= alpha;
@@ -505,6 +560,38 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                                  fz_ld_b16(Pw + row * PSTR8 + 16 * ch));
             }
             fz_wave_lds_sync();
+        }
+        if (MODE == FZ_ATTN_CAPTURE8U && !(ABL & 2) && p_vec) {
+            // as above (after the stash).  Paired: the second tile of a pair flushes both as full 128-byte row segments (8 lanes per
+            // row, 8 rows per pass); a slot's lone last tile (odd number of tiles) leaves as 64-byte segments.  A pair never spans
+            // two kv slots, so its 128 bytes are contiguous in the stored row.  All conditions are wave-uniform.
+            const uint8_t* Pw = reinterpret_cast<const uint8_t*>(smem + 2 * C::STAGE) + wave * 32 * C::PB;
+            uint8_t* const pbase = p8 + (int64_t)(fl + d.p_frame_off) * d.p_frame_stride + (int64_t)h * d.p_head_stride +
+                                   (int64_t)j * d.lkf;
+            const int ti = kt % tps;
+            if (PAIR && (ti & 1)) {
+                const int rb = r0 - KVBLK;  // first key of the pair
+                fz_wave_lds_sync();
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = 8 * i + (lane >> 3), ch = lane & 7;
+                    const int qg = qt * QBLK + wave * 32 + row;
+                    if (qg < d.lq && rb + 16 * ch < d.lkf)
+                        fz_st_b16_nt(pbase + (int64_t)qg * d.p_row_stride + rb + 16 * ch, fz_ld_b16(Pw + fz_p8u_off(row, ch)));
+                }
+                fz_wave_lds_sync();
+            } else if (!PAIR || ti == tps - 1) {
+                fz_wave_lds_sync();
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int row = 16 * i + (lane >> 2), ch = lane & 3;
+                    const int qg = qt * QBLK + wave * 32 + row;
+                    if (qg < d.lq && r0 + 16 * ch < d.lkf)
+                        fz_st_b16_nt(pbase + (int64_t)qg * d.p_row_stride + r0 + 16 * ch,
+                                     fz_ld_b16(Pw + (PAIR ? fz_p8u_off(row, ch) : row * C::PB + 16 * ch)));
+                }
+                fz_wave_lds_sync();
+            }
         }
         __syncthreads();
     }
@@ -560,6 +647,12 @@ static int launch_self(const FzAttnSelfDesc& d, const void* q, const void* k, co
         case FZ_ATTN_INJECT8:
             FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_INJECT8>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
             break;
+        case FZ_ATTN_CAPTURE8U:
+            FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_CAPTURE8U>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
+            break;
+        case FZ_ATTN_INJECT8U:
+            FZ_LAUNCH((attn_self_kernel<D, FZ_ATTN_INJECT8U>), grid, block, 0, stream, d, q_, k_, vt_, o_, p_, row_mask);
+            break;
         default:
             return FZ_ERR_BAD_ARG;
     }
@@ -575,7 +668,8 @@ extern "C" int fz_attn_self(const FzAttnSelfDesc* desc, const void* q, const voi
     const FzAttnSelfDesc& d = *desc;
     if (d.n_frames <= 0 || d.lq <= 0 || d.lkf <= 0 || d.n_kv < 1 || d.n_kv > FZ_MAX_KV_SLOTS) return FZ_ERR_BAD_ARG;
     if (d.mode != FZ_ATTN_FLASH && !p) return FZ_ERR_BAD_ARG;
-    if (!((d.mode == FZ_ATTN_INJECT || d.mode == FZ_ATTN_INJECT8) && row_mask == nullptr) && !k) return FZ_ERR_BAD_ARG;
+    const bool inject = d.mode == FZ_ATTN_INJECT || d.mode == FZ_ATTN_INJECT8 || d.mode == FZ_ATTN_INJECT8U;
+    if (!(inject && row_mask == nullptr) && !k) return FZ_ERR_BAD_ARG;
     if ((d.q_row_stride | d.k_row_stride | d.vt_chan_stride | d.o_row_stride | d.q_frame_stride | d.k_frame_stride |
          d.vt_frame_stride | d.o_frame_stride) & 7)
         return FZ_ERR_BAD_ARG;  // 16-byte vector access

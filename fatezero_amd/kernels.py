@@ -13,7 +13,9 @@ from . import _native as N
 
 FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = N.FZ_ATTN_FLASH, N.FZ_ATTN_CAPTURE, N.FZ_ATTN_INJECT
 FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8 = N.FZ_ATTN_CAPTURE8, N.FZ_ATTN_INJECT8
+FZ_ATTN_CAPTURE8U, FZ_ATTN_INJECT8U = N.FZ_ATTN_CAPTURE8U, N.FZ_ATTN_INJECT8U
 MAP8_DTYPES = (torch.uint8, torch.float8_e5m2)  # storage of an E5M2 self-attention map (one byte per probability)
+MAP8_FORMATS = ("e5m2", "ue4m4")  # what a torch.uint8 map may hold: the tensor alone cannot say which (self_mode_for)
 CROSS_P_STRIDE = N.FZ_CROSS_P_STRIDE
 CROSS_KEYS = N.FZ_CROSS_MAX_KEYS
 TEMPORAL_MAX_FRAMES = N.FZ_TEMPORAL_MAX_FRAMES
@@ -72,9 +74,28 @@ def half_to_e5m2(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.float16).to(torch.float8_e5m2).view(torch.uint8)
 
 
-def self_mode_for(mode: int, p: Optional[torch.Tensor]) -> int:
-    """FZ_ATTN_CAPTURE / FZ_ATTN_INJECT, or their 8-bit forms when `p` is an E5M2 map."""
+def ue4m4_to_half(b: torch.Tensor) -> torch.Tensor:
+    """The fp16 tensor a UE4M4 map stands for (exact: byte b is the half with the bit pattern b << 6)."""
+    if b.dtype != torch.uint8:
+        raise TypeError("a UE4M4 map is torch.uint8 storage, got %s" % b.dtype)
+    return b.to(torch.int16).bitwise_left_shift(6).view(torch.float16)
+
+
+def half_to_ue4m4(x: torch.Tensor) -> torch.Tensor:
+    """fp16 probabilities (bit patterns 0 .. 0x3C00) -> UE4M4 bytes, round-to-nearest-even on the bit pattern: what FZ_ATTN_CAPTURE8U
+    stores for the fp16 map FZ_ATTN_CAPTURE stores.  Integer arithmetic on the int16 view (no torch dtype has this layout)."""
+    h = x.to(torch.float16).contiguous().view(torch.int16)
+    return ((h + 0x1F + ((h >> 6) & 1)) >> 6).to(torch.uint8)
+
+
+def self_mode_for(mode: int, p: Optional[torch.Tensor], map8_format: str = "e5m2") -> int:
+    """FZ_ATTN_CAPTURE / FZ_ATTN_INJECT, or their 8-bit forms when `p` is an 8-bit map.  A torch.uint8 tensor cannot say which 8-bit
+    format it holds: it is E5M2 unless the caller passes map8_format="ue4m4" (never guessed)."""
+    if map8_format not in MAP8_FORMATS:
+        raise ValueError("map8_format must be one of %s, got %r" % (", ".join(repr(m) for m in MAP8_FORMATS), map8_format))
     if p is not None and p.dtype in MAP8_DTYPES:
+        if map8_format == "ue4m4":
+            return {FZ_ATTN_CAPTURE: FZ_ATTN_CAPTURE8U, FZ_ATTN_INJECT: FZ_ATTN_INJECT8U}.get(mode, mode)
         return {FZ_ATTN_CAPTURE: FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT: FZ_ATTN_INJECT8}.get(mode, mode)
     return mode
 
@@ -114,7 +135,8 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
               q_log2_scaled: bool = False, kv_slots_override: Optional[Tuple[List[int], List[int]]] = None,
               kv_clip_len: int = 0, kv_frame_off: int = 0):
     """q,k,out: [N, L, >=C] views with row stride (token-major); vt: [N, C, Lpad]; p: [Fp, heads, Lq, Lk] fp16 -- or, for
-    mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8, the same shape in one-byte storage (torch.uint8 or torch.float8_e5m2: E5M2).
+    mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8, the same shape in one-byte storage (torch.uint8 or torch.float8_e5m2: E5M2); for mode
+    FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U, torch.uint8 storage only (UE4M4: a float8_e5m2 tensor claims the other format).
     k_head_major (optional): K as a contiguous [N, heads, L, d] tensor (fully coalesced key tiles) instead of `k`.
 
     q_log2_scaled: q already carries scale*log2(e) (folded into the projection weight), see include/fatezero_hip.h.
@@ -126,15 +148,22 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
     N_, lq, c = q.shape
     d_head = c // heads
     assert d_head in SUPPORTED_HEAD_DIMS, d_head
-    map8 = mode in (FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8)
-    if map8:
+    map8u = mode in (FZ_ATTN_CAPTURE8U, FZ_ATTN_INJECT8U)
+    map8 = map8u or mode in (FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8)
+    if map8u:
+        if p is None or p.dtype != torch.uint8:
+            raise TypeError("FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U take the map as torch.uint8 storage (UE4M4), got %s"
+                            % (None if p is None else p.dtype))
+        _chk16(q, k, vt, out)
+    elif map8:
         if p is None or p.dtype not in MAP8_DTYPES:
             raise TypeError("FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8 take the map as torch.uint8 or torch.float8_e5m2 storage, got %s"
                             % (None if p is None else p.dtype))
         _chk16(q, k, vt, out)
     else:
         if p is not None and p.dtype in MAP8_DTYPES:
-            raise TypeError("an 8-bit map needs mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8 (kernels.self_mode_for)")
+            raise TypeError("an 8-bit map needs mode FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8, or FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U "
+                            "for UE4M4 (kernels.self_mode_for)")
         _chk16(q, k, vt, out, p)
     n_frames = N_ - frame0 if n_frames is None else n_frames
     kabs, kval = kv_slots(index_list, clip_len) if kv_slots_override is None else kv_slots_override

@@ -37,12 +37,13 @@ class AttnPlan:
     """What the attention kernels do for one controlled layer call.
 
     Frames [0, n_plain) run plain flash attention; frames [n_plain, N) run `mode` with the given operands."""
-    __slots__ = ("n_plain", "mode", "p", "row_mask", "mapper_t", "coef", "cur_out", "capture_first")
+    __slots__ = ("n_plain", "mode", "p", "row_mask", "mapper_t", "coef", "cur_out", "capture_first", "capture_first_format")
 
     def __init__(self, n_plain, mode=K.FZ_ATTN_FLASH, p=None, row_mask=None, mapper_t=None, coef=None, cur_out=None,
-                 capture_first=None):
+                 capture_first=None, capture_first_format="e5m2"):
         self.n_plain, self.mode, self.p, self.row_mask = n_plain, mode, p, row_mask
         self.mapper_t, self.coef, self.cur_out, self.capture_first = mapper_t, coef, cur_out, capture_first
+        self.capture_first_format = capture_first_format  # which 8-bit format a uint8 `capture_first` holds (kernels.self_mode_for)
 
 
 def _plan_for(controller, is_cross, place, n, clip, heads, lq, lk, device):
@@ -416,9 +417,9 @@ class SparseCausalAttention(CrossAttention):
             if plan.n_plain < n:
                 rest = dict(frame0=plan.n_plain, n_frames=n - plan.n_plain)
                 if plan.capture_first is not None:  # edit pass with save_self_attention: keep the live map too
-                    K.attn_self(q, kk, vt, out, mode=K.self_mode_for(K.FZ_ATTN_CAPTURE, plan.capture_first), p=plan.capture_first,
-                                **rest, **kw)
-                if plan.mode in (K.FZ_ATTN_INJECT, K.FZ_ATTN_INJECT8):  # (INJECT8: the stored map is E5M2 bytes)
+                    K.attn_self(q, kk, vt, out, mode=K.self_mode_for(K.FZ_ATTN_CAPTURE, plan.capture_first, plan.capture_first_format),
+                                p=plan.capture_first, **rest, **kw)
+                if plan.mode in (K.FZ_ATTN_INJECT, K.FZ_ATTN_INJECT8, K.FZ_ATTN_INJECT8U):  # (INJECT8 / INJECT8U: the stored map is bytes)
                     K.attn_self(q, kk if plan.row_mask is not None else None, vt, out, mode=plan.mode, p=plan.p,
                                 row_mask=plan.row_mask, **rest, **kw)
                 elif not (plan.mode == K.FZ_ATTN_FLASH and plan.capture_first is not None):

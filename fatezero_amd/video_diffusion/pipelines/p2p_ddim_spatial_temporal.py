@@ -64,8 +64,8 @@ class _LatentState:
 
 class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, disk_store: bool = False, map_dtype: str = "fp16"):
-        """`map_dtype` (extension): "fp16" (default) or "e5m2" -- the captured SELF-attention maps at one byte per probability, which
-        halves the map arena (attention_store.py); cross maps, the inversion trajectory and every other tensor are unaffected."""
+        """`map_dtype` (extension): "fp16" (default), "e5m2" or "ue4m4" -- the captured SELF-attention maps at one byte per probability, which
+        halves the map arena (attention_store.py; "ue4m4" keeps 4 mantissa bits where "e5m2" keeps 2); cross maps, the inversion trajectory and every other tensor are unaffected."""
         super().__init__(vae, text_encoder, tokenizer, unet, scheduler)
         self.map_dtype = self.default_map_dtype = map_dtype  # (default_map_dtype: what a YAML config without the key falls back to)
         self.store_controller = attention_util.AttentionStore(disk_store=disk_store, map_dtype=map_dtype)
@@ -84,7 +84,7 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         return [full[i].contiguous() for i in range(s_)]
 
     def set_map_dtype(self, map_dtype: str):
-        """Switch the storage of the captured self-attention maps ("fp16" | "e5m2") for the jobs that follow: the maps of the last
+        """Switch the storage of the captured self-attention maps ("fp16" | "e5m2" | "ue4m4") for the jobs that follow: the maps of the last
         inversion are dropped and a store of the new format takes the old one's place."""
         if map_dtype != self.map_dtype:
             store = self.store_controller.with_map_dtype(map_dtype)  # (raises on an unknown name)

@@ -20,6 +20,9 @@ instead of writing .pt files.
 attention kernel rounds each fp16 value to E5M2 -- the top byte of the half -- as it writes (FZ_ATTN_CAPTURE8) and the edit reads the bytes
 back (FZ_ATTN_INJECT8).  Cross maps stay fp16.  Every reference-shaped reader (`attention_store_all_step`, `CapturedMap.view`, the running
 sum with `accumulate_self`) sees fp16 tensors dequantised exactly from the bytes, built when they are read.
+`map_dtype="ue4m4"` is the same arena with the byte holding bits 13..6 of the half instead of bits 15..8 (a probability never sets bits 15
+and 14): 4 mantissa bits instead of 2 (FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U).  A uint8 slab does not say which format it holds: every
+CapturedMap carries its format.
 """
 import abc
 import math
@@ -32,7 +35,7 @@ from ... import kernels as K
 from ..models.attention import AttnPlan
 
 KEYS = ("down_cross", "mid_cross", "up_cross", "down_self", "mid_self", "up_self")
-MAP_DTYPES = ("fp16", "e5m2")  # storage of the captured self-attention maps
+MAP_DTYPES = ("fp16", "e5m2", "ue4m4")  # storage of the captured self-attention maps
 MAX_CONTROLLED_TOKENS = 32 ** 2  # attention_store.py:83, attention_util.py:104
 
 
@@ -395,21 +398,35 @@ def _numel(shape):
 
 class CapturedMap:
     """One captured map: `storage` is what the kernels address ([F, heads, Lq, 80] for cross maps), `view` is the
-    reference-shaped tensor handed to users ([F, heads, Lq, 77]).  An 8-bit self map (`map_dtype="e5m2"`) has uint8 `storage`;
-    its `view` is the fp16 tensor the bytes stand for, dequantised (exactly) at every read -- no fp16 copy is kept."""
-    __slots__ = ("storage", "lk", "_view")
+    reference-shaped tensor handed to users ([F, heads, Lq, 77]).  An 8-bit self map (`map_dtype="e5m2"` / "ue4m4") has uint8 `storage`;
+    its `view` is the fp16 tensor the bytes stand for, dequantised (exactly) at every read -- no fp16 copy is kept.  `fmt` names what
+    the bytes are ("fp16" | "e5m2" | "ue4m4"; 8-bit storage without a name is E5M2)."""
+    __slots__ = ("storage", "lk", "fmt", "_view")
 
-    def __init__(self, storage, lk):
+    def __init__(self, storage, lk, fmt=None):
         self.storage, self.lk = storage, lk
+        self.fmt = fmt if fmt is not None else ("e5m2" if self.is_8bit else "fp16")
+        assert (self.fmt != "fp16") == self.is_8bit and self.fmt in MAP_DTYPES, (self.fmt, storage.dtype)
         self._view = None if self.is_8bit else (storage[..., :lk] if storage.shape[-1] != lk else storage)
 
     @property
     def is_8bit(self):
         return self.storage.dtype in K.MAP8_DTYPES
 
+    @property
+    def map8_format(self):
+        """The `map8_format` of kernels.self_mode_for (without meaning for an fp16 map)."""
+        return self.fmt if self.is_8bit else "e5m2"
+
     def half(self):
         """`storage` as fp16 (itself, or the dequantised bytes)."""
+        if self.fmt == "ue4m4":
+            return K.ue4m4_to_half(self.storage)
         return K.e5m2_to_half(self.storage) if self.is_8bit else self.storage
+
+    def quantise(self, attn):
+        """An fp16 map as this 8-bit map's bytes, rounded the way the capture kernel of its format rounds."""
+        return K.half_to_ue4m4(attn) if self.fmt == "ue4m4" else K.half_to_e5m2(attn)
 
     @property
     def view(self):
@@ -472,7 +489,7 @@ class AttentionStore(AttentionControl):
         super().__init__()
         if map_dtype not in MAP_DTYPES:
             raise ValueError("map_dtype must be one of %s, got %r" % (", ".join(repr(m) for m in MAP_DTYPES), map_dtype))
-        self.map_dtype = map_dtype  # "e5m2": self-attention maps at one byte per probability (cross maps stay fp16)
+        self.map_dtype = map_dtype  # "e5m2" / "ue4m4": self-attention maps at one byte per probability (cross maps stay fp16)
         # The reference's disk_store=True writes every step's maps to ./trash/attention_cache_*/NNN.pt and loads them back in the edit
         # (attention_store.py:103-108, attention_util.py:115-116).  Here it switches the arena's spill tier on: steps stay in HBM while they
         # fit (`hbm_budget_bytes`, or FZ_ARENA_HBM_GB, or 90 % of what the device has free), the rest goes to pinned host memory behind the
@@ -511,10 +528,11 @@ class AttentionStore(AttentionControl):
     def new_slot(self, key, frames, heads, lq, lk, is_cross, device) -> CapturedMap:
         width = K.CROSS_P_STRIDE if is_cross else lk
         self._device = device
-        map8 = self.map_dtype == "e5m2" and not is_cross
-        cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device, itemsize=1 if map8 else 2), lk)
+        map8 = self.map_dtype != "fp16" and not is_cross
+        cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device, itemsize=1 if map8 else 2), lk,
+                         self.map_dtype if map8 else "fp16")
         self._step_maps[key].append(cm)
-        if self.map_dtype == "e5m2":
+        if self.map_dtype != "fp16":
             if not isinstance(self.step_store, LazyStepMaps):
                 self.step_store = LazyStepMaps(self.step_store)
             self.step_store.raw(key).append(cm if map8 else cm.view)  # 8-bit entries are read back as fp16, dequantised at the read
@@ -527,7 +545,7 @@ class AttentionStore(AttentionControl):
             return AttnPlan(0)
         key = f"{place}_{'cross' if is_cross else 'self'}"
         cm = self.new_slot(key, n_ctrl, heads, lq, lk, is_cross, device)
-        return AttnPlan(0, K.self_mode_for(K.FZ_ATTN_CAPTURE, cm.storage), p=cm.storage)
+        return AttnPlan(0, K.self_mode_for(K.FZ_ATTN_CAPTURE, cm.storage, cm.map8_format), p=cm.storage)
 
     @property
     def issue_events_first(self):
@@ -548,7 +566,7 @@ class AttentionStore(AttentionControl):
             if cm.storage.shape[-1] != lk:
                 cm.storage[..., lk:] = 0
             if cm.is_8bit:
-                cm.storage.copy_(K.half_to_e5m2(attn))
+                cm.storage.copy_(cm.quantise(attn))
             else:
                 cm.view.copy_(attn)
         return attn
@@ -600,15 +618,16 @@ class AttentionStore(AttentionControl):
             for cm in maps[k]:
                 layout.append((k, cm.storage.data_ptr() - base, tuple(cm.storage.shape), cm.lk, cm.storage.element_size()))
         sp = self.arena.spill_step(layout, slab.device)
-        self.attention_store_all_step[step] = HostStepMaps({k: _views(v) for k, v in self._maps_over(sp.host, layout).items()}, sp)
+        self.attention_store_all_step[step] = HostStepMaps({k: _views(v) for k, v in self._maps_over(sp.host, layout, self.map_dtype).items()}, sp)
         self._all_step_maps[step] = None  # resolved through the arena from here on (maps_of_step)
 
     @staticmethod
-    def _maps_over(slab, layout):
+    def _maps_over(slab, layout, map_dtype="e5m2"):
         out = {k: [] for k in KEYS}
-        for k, off, shape, lk, itemsize in layout:  # (the 8-bit slabs travel through the spill tier as they are)
+        for k, off, shape, lk, itemsize in layout:  # (the 8-bit slabs travel through the spill tier as they are: `map_dtype` names them)
             raw = slab[off: off + itemsize * _numel(shape)]
-            out[k].append(CapturedMap((raw.view(torch.float16) if itemsize == 2 else raw).view(shape), lk))
+            out[k].append(CapturedMap((raw.view(torch.float16) if itemsize == 2 else raw).view(shape), lk,
+                                      "fp16" if itemsize == 2 else map_dtype))
         return out
 
     def with_map_dtype(self, map_dtype: str):
@@ -627,7 +646,7 @@ class AttentionStore(AttentionControl):
         if self._fetched[0] != step_in_store:  # a spilled step: into a staging slab of the ring, the next one behind it
             sp = self.arena.spilled[step_in_store]
             slab = self.arena.fetch(step_in_store, self._device)
-            self._fetched = (step_in_store, self._maps_over(slab, sp.layout))
+            self._fetched = (step_in_store, self._maps_over(slab, sp.layout, self.map_dtype))
         return self._fetched[1]
 
     def get_average_attention(self):

@@ -155,9 +155,10 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
                 plan.cur_out = self.new_slot(key, n_ctrl, heads, lq, lk, True, device).storage
             return plan
         if self.save_self_attention:  # only outside the 'swap' flow of the reference's validation loop
-            plan.capture_first = self.new_slot(key, n_ctrl, heads, lq, lk, False, device).storage
+            own = self.new_slot(key, n_ctrl, heads, lq, lk, False, device)
+            plan.capture_first, plan.capture_first_format = own.storage, own.map8_format
         if self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]:
-            plan.mode, plan.p = K.self_mode_for(K.FZ_ATTN_INJECT, base.storage), base.storage  # (INJECT8 over an E5M2 map)
+            plan.mode, plan.p = K.self_mode_for(K.FZ_ATTN_INJECT, base.storage, base.map8_format), base.storage  # (INJECT8 / INJECT8U over an 8-bit map)
             if self.attention_blend is not None:
                 h, w = map_hw(lq, getattr(self, "latent_hw", None))
                 mask = self.attention_blend(target_h=h, target_w=w, attention_store=step_maps, step_in_store=sis)
@@ -316,7 +317,7 @@ def make_controller(tokenizer, prompts: List[str], is_replace_controller: bool, 
                     additional_attention_store=None, use_inversion_attention=False, blend_th=(0.3, 0.3),
                     NUM_DDIM_STEPS=None, blend_latents=False, blend_self_attention=False, save_path=None,
                     save_self_attention=True, disk_store=False, map_dtype="fp16") -> AttentionControlEdit:
-    """attention_util.py:320-387.  `map_dtype` ("fp16" | "e5m2"): storage of the self-attention maps the edit pass itself keeps
+    """attention_util.py:320-387.  `map_dtype` ("fp16" | "e5m2" | "ue4m4"): storage of the self-attention maps the edit pass itself keeps
     (save_self_attention); what it READS is in the format of `additional_attention_store`, whatever this says.  `save_path` feeds the blend-mask PNG dumps (`<save_path>/latent_blend_mask`,
     `<save_path>/attention_blend_mask`, written off the hot loop: spatial_blend.py); unlike the reference, `save_path=None`
     together with `blend_words` is accepted and simply dumps nothing."""

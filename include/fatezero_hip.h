@@ -31,6 +31,14 @@ extern "C" {
  * rounded.  16-byte row pieces need lkf and the three strides to be multiples of 16 (otherwise an element-wise path runs). */
 #define FZ_ATTN_CAPTURE8 3
 #define FZ_ATTN_INJECT8 4
+/* fz_attn_self only: the same two with the map stored as UE4M4 bytes.  A probability lies in [0, 1], so the sign bit and the top
+ * exponent bit of its fp16 pattern (<= 0x3C00) are always 0; the stored byte is bits 13..6 of the half -- unsigned, 4 exponent and
+ * 4 mantissa bits, the range of E5M2 (fp16 subnormals included) at a relative error <= 2^-5 instead of 2^-3 -- rounded to
+ * nearest-even on the fp16 bit pattern: byte = (h + 0x1F + ((h >> 6) & 1)) >> 6, at most 0xF0 (= 1.0).  Reading back is exact:
+ * byte b stands for the half b << 6.  `p`, its strides, the 16-byte conditions and the output `o` of the capture are as for
+ * FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8; the two formats share nothing but the byte size, and a byte does not say which one it is. */
+#define FZ_ATTN_CAPTURE8U 5
+#define FZ_ATTN_INJECT8U 6
 
 #define FZ_MAX_KV_SLOTS 4
 

@@ -240,8 +240,9 @@ def conv64_bench():
 
 
 def self8_bench():
-    """Capture and inject launches with the map in fp16 against E5M2 bytes (FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8), same process, at the 8-frame
-    (inversion) and 16-frame (CFG edit: the launch covers the controlled half) launch shapes of the 32^2 and 16^2 levels."""
+    """Capture and inject launches with the map in fp16 against E5M2 bytes (FZ_ATTN_CAPTURE8 / FZ_ATTN_INJECT8) and UE4M4 bytes
+    (FZ_ATTN_CAPTURE8U / FZ_ATTN_INJECT8U), same process, at the 8-frame (inversion) and 16-frame (CFG edit: the launch covers the
+    controlled half) launch shapes of the 32^2 and 16^2 levels.  `*_speedup` = fp16 ms / e5m2 ms, `*_speedup_ue4m4` = fp16 ms / ue4m4 ms."""
     dev, heads, res = "cuda", 8, {}
     for (lq, c) in [(1024, 640), (256, 1280)]:
         for nf in (8, 16):
@@ -256,16 +257,19 @@ def self8_bench():
             mask = (torch.rand(nf, lq, generator=g) > 0.5).float().to(dev)
             kw = dict(clip_len=nf, heads=heads, index_list=idx)
             tag = f"L{lq}_d{d}_f{nf}"
-            for name, mode, p in (("fp16", K.FZ_ATTN_CAPTURE, p16), ("e5m2", K.FZ_ATTN_CAPTURE8, p8)):
+            for name, mode, p in (("fp16", K.FZ_ATTN_CAPTURE, p16), ("e5m2", K.FZ_ATTN_CAPTURE8, p8),
+                                  ("ue4m4", K.FZ_ATTN_CAPTURE8U, p8)):
                 ms = timeit(lambda: K.attn_self(q, k, vt, out, mode=mode, p=p, **kw))
                 res[f"capture_{tag}_{name}"] = {"ms": ms, "map_GBps": p.numel() * p.element_size() / ms / 1e6}
-            for name, mode, p in (("fp16", K.FZ_ATTN_INJECT, p16), ("e5m2", K.FZ_ATTN_INJECT8, p8)):
+            for name, mode, p in (("fp16", K.FZ_ATTN_INJECT, p16), ("e5m2", K.FZ_ATTN_INJECT8, p8),
+                                  ("ue4m4", K.FZ_ATTN_INJECT8U, p8)):
                 ms = timeit(lambda: K.attn_self(q, None, vt, out, mode=mode, p=p, **kw))
                 res[f"inject_nomask_{tag}_{name}"] = {"ms": ms, "map_GBps": p.numel() * p.element_size() / ms / 1e6}
                 ms = timeit(lambda: K.attn_self(q, k, vt, out, mode=mode, p=p, row_mask=mask, **kw))
                 res[f"inject_mask_{tag}_{name}"] = {"ms": ms}
             for kind in ("capture", "inject_nomask", "inject_mask"):
                 res[f"{kind}_{tag}_speedup"] = res[f"{kind}_{tag}_fp16"]["ms"] / res[f"{kind}_{tag}_e5m2"]["ms"]
+                res[f"{kind}_{tag}_speedup_ue4m4"] = res[f"{kind}_{tag}_fp16"]["ms"] / res[f"{kind}_{tag}_ue4m4"]["ms"]
     print(json.dumps(res, indent=1))
     return res
 

@@ -19,7 +19,7 @@ argument taken out of its name, and the value it had there is shown for the kern
 import re
 import sys
 
-MODES = {0: "FLASH", 1: "CAPTURE", 2: "INJECT", 3: "CAPTURE8", 4: "INJECT8"}
+MODES = {0: "FLASH", 1: "CAPTURE", 2: "INJECT", 3: "CAPTURE8", 4: "INJECT8", 5: "CAPTURE8U", 6: "INJECT8U"}
 
 
 def kernels(path, prefix="_Z16attn_self_kernel"):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Same-process A/B of bench.py's job with the captured self-attention maps in fp16 and in E5M2 (`map_dtype="e5m2"`): one JSON line with the
-time of each job, `arena_bytes()` of each store, and the distance between the two edited latents relative to the latent scale.
+"""Same-process A/B of bench.py's job with the captured self-attention maps in fp16, in E5M2 (`map_dtype="e5m2"`) and in UE4M4 (`"ue4m4"`): one
+JSON line with the time of each job, `arena_bytes()` of each store, and the distance of each 8-bit job's edited latents from the fp16-arena
+job's, relative to the latent scale (the `edited_*` keys at the top level are the E5M2 job's, as before; `ue4m4_vs_fp16` holds the other's).
 
 The job is bench.py's (jeep -> Porsche, capture inversion + 1 CFG edit with Replace and blend-masked self-attention, 8 frames x 512^2 x
 (50 + 50) DDIM steps by default, latents in / out); bench.py itself is imported, not changed.
@@ -39,6 +40,9 @@ def run_job(pipe, z0, ddim_steps, device, map_dtype, blend_th=None):
     return out["sdimage_output"].images
 
 
+FORMATS = ("fp16", "e5m2", "ue4m4")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=1, help="timed jobs per format (after one untimed warm-up job each)")
@@ -53,7 +57,7 @@ def main():
     L = args.latent_size
     z0 = torch.randn(1, 4, args.frames, L, L, generator=torch.Generator().manual_seed(1234)).to(device)
     res = {}
-    for fmt in ("fp16", "e5m2", "fp16", "e5m2")[: 2 if args.jobs == 1 else 4]:  # (interleaved: clocks drift over minutes)
+    for fmt in (FORMATS * 2)[: len(FORMATS) if args.jobs == 1 else 2 * len(FORMATS)]:  # (interleaved: clocks drift over minutes)
         if fmt not in res:
             run_job(pipe, z0, args.ddim_steps, device, fmt, args.blend_th)  # warm-up: allocations, plans
             res[fmt] = {"ms": []}
@@ -68,16 +72,22 @@ def main():
         res[fmt]["edited"] = edited.float().cpu()
         res[fmt]["arena_bytes"] = int(pipe.store_controller.arena_bytes)
         res[fmt]["arena_step_bytes"] = int(pipe.store_controller.arena.step_bytes)
-    a, b = res["fp16"].pop("edited"), res["e5m2"].pop("edited")
+    a, b, c = res["fp16"].pop("edited"), res["e5m2"].pop("edited"), res["ue4m4"].pop("edited")
     scale = float(a.abs().max())
-    diff = (a - b).abs()
+
+    def deviation(x):
+        diff = (a - x).abs()
+        return {"edited_max_abs_diff": float(diff.max()), "edited_max_diff_over_scale": float(diff.max()) / scale,
+                "edited_q99_diff_over_scale": float(torch.quantile(diff.flatten()[:: max(1, diff.numel() // 1000000)], 0.99)) / scale,
+                "edited_rms_diff_over_scale": float(diff.pow(2).mean().sqrt()) / scale}
     line = {"blend_th": args.blend_th, "stored_rows_fraction": bench.stored_rows_fraction(pipe), "job": f"{args.frames}f x {8 * L}^2 x {args.ddim_steps} + {args.ddim_steps} DDIM steps (bench.py's job)", "fp16": res["fp16"], "e5m2": res["e5m2"],
+            "ue4m4": res["ue4m4"],
             "arena_ratio": res["e5m2"]["arena_bytes"] / res["fp16"]["arena_bytes"],
+            "arena_ratio_ue4m4": res["ue4m4"]["arena_bytes"] / res["fp16"]["arena_bytes"],
             "time_ratio_e5m2_over_fp16": min(res["e5m2"]["ms"]) / min(res["fp16"]["ms"]),
-            "edited_latent_scale": scale, "edited_max_abs_diff": float(diff.max()), "edited_max_diff_over_scale": float(diff.max()) / scale,
-            "edited_q99_diff_over_scale": float(torch.quantile(diff.flatten()[:: max(1, diff.numel() // 1000000)], 0.99)) / scale,
-            "edited_rms_diff_over_scale": float(diff.pow(2).mean().sqrt()) / scale,
-            "outputs_finite": bool(torch.isfinite(a).all() and torch.isfinite(b).all())}
+            "time_ratio_ue4m4_over_fp16": min(res["ue4m4"]["ms"]) / min(res["fp16"]["ms"]),
+            "edited_latent_scale": scale, **deviation(b), "ue4m4_vs_fp16": deviation(c),
+            "outputs_finite": bool(torch.isfinite(a).all() and torch.isfinite(b).all() and torch.isfinite(c).all())}
     print(json.dumps(line), flush=True)
 
 
