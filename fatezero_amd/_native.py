@@ -18,6 +18,8 @@ FZ_MAX_KV_SLOTS = 4
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80
 FZ_TEMPORAL_MAX_FRAMES = 512
+FZ_LATENT_F32, FZ_LATENT_F16 = 0, 1  # fz_latent_tokens: element type of the stored latent
+FZ_ERR_BAD_ARG = -1
 
 
 class FzAttnSelfDesc(C.Structure):
@@ -138,6 +140,7 @@ _SIGS = {
     "fz_softmax_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_float, _P]),
     "fz_transpose_pad": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P]),
     "fz_latent_update": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "fz_latent_tokens": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "fz_accumulate": (C.c_int, [_P, _P, C.c_int64, _P]),
     "fz_repeat": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "fz_peer_put": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_uint32, _P, _P]),

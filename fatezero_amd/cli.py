@@ -104,7 +104,8 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
     pipeline = instantiate_from_config(test_pipeline_config, vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet,
                                        scheduler=DDIMScheduler.from_pretrained(pretrained_model_path, subfolder="scheduler"),
                                        disk_store=kwargs.get("disk_store", False),
-                                       map_dtype=config_driver.map_dtype_of(editing_config, kwargs.get("map_dtype")))
+                                       map_dtype=config_driver.map_dtype_of(editing_config, kwargs.get("map_dtype")),
+                                       recompute_maps=config_driver.recompute_maps_of(editing_config, kwargs.get("recompute_maps")))
     pipeline.scheduler.set_timesteps(editing_config["num_inference_steps"])
     pipeline.set_progress_bar_config(disable=True)
     pipeline.print_pipeline(logger)
@@ -181,8 +182,14 @@ def run():
                   help="storage of the captured self-attention maps (default: editing_config.attention_map_dtype, else fp16)")
     @click.option("--image-size", type=int, nargs=2, default=None, metavar="HEIGHT WIDTH",
                   help="frame size of a rectangular clip (default: dataset_config.image_size, an int or a [height, width] pair)")
-    def _main(config, map_dtype, image_size):
-        run_config_file(config, image_size=image_size, **({} if map_dtype is None else {"map_dtype": map_dtype}))
+    @click.option("--recompute-maps/--no-recompute-maps", default=None,
+                  help="keep the inversion's latents instead of its attention maps and recompute each step's maps during the edit "
+                       "(default: editing_config.recompute_attention_maps, else off)")
+    def _main(config, map_dtype, image_size, recompute_maps):
+        over = {} if map_dtype is None else {"map_dtype": map_dtype}
+        if recompute_maps is not None:
+            over["recompute_maps"] = recompute_maps
+        run_config_file(config, image_size=image_size, **over)
 
     _main()
 

@@ -104,6 +104,19 @@ def map_dtype_of(editing_config: Optional[Dict[str, Any]], override: Optional[st
     return value
 
 
+def recompute_maps_of(editing_config: Optional[Dict[str, Any]], override: Optional[bool] = None) -> bool:
+    """The pipeline's `recompute_maps` mode: `override` (the --recompute-maps switch), else the optional
+    `editing_config.recompute_attention_maps` key (an extension: no reference config has it), else off.  The mode re-runs inversion
+    forwards, so it needs `use_inversion_attention: True`."""
+    value = override if override is not None else (editing_config or {}).get("recompute_attention_maps", False)
+    if not isinstance(value, bool):
+        raise ValueError("recompute_attention_maps must be true or false, got %r" % (value,))
+    if value and editing_config is not None and not editing_config.get("use_inversion_attention", False):
+        raise ValueError("recompute_attention_maps: true needs use_inversion_attention: true (with use_inversion_attention: false the stored "
+                         "maps come from an edit pass, there is no inversion forward to recompute them from)")
+    return value
+
+
 def image_size_of(dataset_config: Optional[Dict[str, Any]]):
     """`dataset_config.image_size`: an int (square frames, the reference's form) or a `[height, width]` pair (an extension: a clip edited at
     its own aspect ratio).  Returns the int, or the pair as a tuple of ints; 512 when the key is absent (the dataset's default)."""
@@ -156,6 +169,8 @@ def run_config(pipe, config: Dict[str, Any], *, latents: Optional[torch.Tensor] 
     pipe.scheduler.set_timesteps(steps)
     if hasattr(pipe, "set_map_dtype"):  # the key is optional: without it the format the pipeline was built with applies (again)
         pipe.set_map_dtype(map_dtype_of(editing) if "attention_map_dtype" in editing else pipe.default_map_dtype)
+    if hasattr(pipe, "set_recompute_maps"):  # (likewise: without the key, the mode the pipeline was built with)
+        pipe.set_recompute_maps(recompute_maps_of(editing) if "recompute_attention_maps" in editing else pipe.default_recompute_maps)
     init = None
     inverted = None
     if editing.get("use_invertion_latents", False):  # (sic) the reference's spelling

@@ -188,6 +188,36 @@ extern "C" int fz_latent_update(float* z, const void* eps_u, const void* eps_c, 
     return fz_last_launch_status();
 }
 
+// ---- tok[f][pix][c] = (half) z[c][f][pix]: a stored latent as the UNet's token-major input (the per-step source forward of the
+//      recompute_maps mode).  One thread per token: four loads that are coalesced across the wave per channel plane, one 8-byte store.
+//      The cast is the one latent_update_kernel writes next_in with (round to nearest even), so a latent that went through
+//      z -> next_in and the same latent read back from the store give the same bytes.
+template <typename T>
+FZ_KERNEL void __launch_bounds__(256)
+latent_tokens_kernel(const T* __restrict__ z, half_t* __restrict__ tok, int frames, int hw) {
+    const int64_t total = (int64_t)frames * hw;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    half4_t o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = (half_t)(float)z[(int64_t)c * total + i];
+    *reinterpret_cast<half4_t*>(tok + i * 4) = o;
+}
+
+extern "C" int fz_latent_tokens(const void* z, int z_dtype, void* tok, int frames, int hw, void* stream) {
+    if (!z || !tok || frames <= 0 || hw <= 0) return FZ_ERR_BAD_ARG;
+    if (z_dtype != FZ_LATENT_F32 && z_dtype != FZ_LATENT_F16) return FZ_ERR_BAD_ARG;
+    if (((uintptr_t)tok & 7) || ((uintptr_t)z & (z_dtype == FZ_LATENT_F32 ? 3 : 1)) || z == tok) return FZ_ERR_BAD_ARG;
+    const int64_t total = (int64_t)frames * hw;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffLL) return FZ_ERR_BAD_ARG;
+    if (z_dtype == FZ_LATENT_F32)
+        FZ_LAUNCH(latent_tokens_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)z, (half_t*)tok, frames, hw);
+    else
+        FZ_LAUNCH(latent_tokens_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (const half_t*)z, (half_t*)tok, frames, hw);
+    return fz_last_launch_status();
+}
+
 // ---- acc (fp32) += x (fp16): running sum of the edit pass' own cross maps (attention_store.py:95-101) ---------
 FZ_KERNEL void __launch_bounds__(256) accumulate_kernel(float* __restrict__ acc, const half_t* __restrict__ x, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {

@@ -311,7 +311,8 @@ class IssuePlans:
             if sig is None:
                 return None
         return (tuple(x.data.shape), x.b, x.rep, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
-                ctx.dtype, type(controller), sig, _model_switches())  # (sig carries the map format)
+                ctx.dtype, type(controller), sig, _model_switches(),  # (sig carries the map format)
+                getattr(self.unet, "_maps_up_to", None))  # (a forward that ends behind its last captured map is another launch list)
 
     # -- record --------------------------------------------------------------------------------------------
     @classmethod
@@ -365,8 +366,10 @@ class IssuePlans:
         ctx_kv = []
         for m in self.unet.modules():
             if isinstance(m, CrossAttention) and m._ctx_kv is not None:
-                if m._ctx_kv[0] is not ctx:  # (cannot happen: the recorded forward just attended to ctx)
-                    raise RuntimeError("issue plan: a cross-attention layer holds the projections of another context")
+                if m._ctx_kv[0] is not ctx:
+                    if getattr(self.unet, "_maps_up_to", None) is not None:
+                        continue  # a layer behind the exit of a maps-only forward: it did not run, its cache is an earlier forward's
+                    raise RuntimeError("issue plan: a cross-attention layer holds the projections of another context")  # (cannot happen: the recorded forward just attended to ctx)
                 ctx_kv.append((m, m._ctx_kv[2], m._ctx_kv[3], m._ctx_kv[4]))
         if len(self.plans) >= self.MAX_PLANS:
             self.plans.pop(next(iter(self.plans)))

@@ -1111,6 +1111,25 @@ def latent_update(z: torch.Tensor, eps_u: Optional[torch.Tensor], eps_c: torch.T
     return z
 
 
+def latent_tokens(z: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z: a latent [4, F, hw] (fp32 or fp16, contiguous) -> the UNet's token-major fp16 input [F, hw, 4], rounded to nearest even
+    (fz_latent_tokens): what `z.permute(1, 2, 0).to(torch.float16)` computes, in one library launch."""
+    if z.dim() != 3 or z.shape[0] != 4 or z.dtype not in (torch.float32, torch.float16) or not z.is_contiguous():
+        raise ValueError("fz_latent_tokens: a contiguous fp32 / fp16 latent [4, F, hw], got %s %s" % (tuple(z.shape), z.dtype))
+    _, frames, hw = z.shape
+    if out is None:
+        out = torch.empty(frames, hw, 4, dtype=torch.float16, device=z.device)
+    if out.dtype != torch.float16 or tuple(out.shape) != (frames, hw, 4) or not out.is_contiguous() or out.device != z.device:
+        raise ValueError("fz_latent_tokens: the output is a contiguous fp16 [F, hw, 4] tensor on the latent's device")
+    if out.data_ptr() % 8 or z.data_ptr() % z.element_size():
+        raise ValueError("fz_latent_tokens: the tokens need 8-byte alignment, the latent its element's")
+    rc = N.lib().fz_latent_tokens(_ptr(z), N.FZ_LATENT_F32 if z.dtype == torch.float32 else N.FZ_LATENT_F16, _ptr(out), frames, hw,
+                                  _stream(z))
+    if rc:
+        N.check(rc, "fz_latent_tokens")
+    return out
+
+
 def accumulate(acc: torch.Tensor, x: torch.Tensor):
     assert acc.dtype == torch.float32 and x.dtype == torch.float16 and acc.numel() == x.numel()
     assert acc.is_contiguous() and x.is_contiguous()

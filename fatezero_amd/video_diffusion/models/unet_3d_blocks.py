@@ -118,12 +118,13 @@ class CrossAttnUpBlockPseudo3D(nn.Module):
             self.upsamplers = nn.ModuleList([UpsamplePseudo3D(out_channels, use_conv=True, out_channels=out_channels,
                                                               model_config=model_config)])
 
-    def forward_tokens(self, x: Tokens, skips, temb_act, ctx):
+    def forward_tokens(self, x: Tokens, skips, temb_act, ctx, upsample=True):
+        """upsample=False: stop behind the last transformer (a forward that is only run for its attention maps, unet_3d_condition.py)."""
         x = x.expanded()
         for resnet, attn in zip(self.resnets, self.attentions):
             x = resnet.forward_tokens(_cat_skip(x, skips.pop()), temb_act)
             x = attn.forward_tokens(x, ctx)
-        if self.upsamplers is not None:
+        if self.upsamplers is not None and upsample:
             x = self.upsamplers[0].forward_tokens(x)
         return x
 
@@ -146,11 +147,11 @@ class UpBlockPseudo3D(nn.Module):
             self.upsamplers = nn.ModuleList([UpsamplePseudo3D(out_channels, use_conv=True, out_channels=out_channels,
                                                               model_config=model_config)])
 
-    def forward_tokens(self, x: Tokens, skips, temb_act, ctx=None):
+    def forward_tokens(self, x: Tokens, skips, temb_act, ctx=None, upsample=True):
         x = x.expanded()
         for resnet in self.resnets:
             x = resnet.forward_tokens(_cat_skip(x, skips.pop()), temb_act)
-        if self.upsamplers is not None:
+        if self.upsamplers is not None and upsample:
             x = self.upsamplers[0].forward_tokens(x)
         return x
 

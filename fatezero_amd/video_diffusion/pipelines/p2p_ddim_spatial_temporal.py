@@ -63,12 +63,19 @@ class _LatentState:
 
 
 class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
-    def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, disk_store: bool = False, map_dtype: str = "fp16"):
+    def __init__(self, vae, text_encoder, tokenizer, unet, scheduler, disk_store: bool = False, map_dtype: str = "fp16",
+                 recompute_maps: bool = False):
         """`map_dtype` (extension): "fp16" (default), "e5m2" or "ue4m4" -- the captured SELF-attention maps at one byte per probability, which
-        halves the map arena (attention_store.py; "ue4m4" keeps 4 mantissa bits where "e5m2" keeps 2); cross maps, the inversion trajectory and every other tensor are unaffected."""
+        halves the map arena (attention_store.py; "ue4m4" keeps 4 mantissa bits where "e5m2" keeps 2); cross maps, the inversion trajectory and every other tensor are unaffected.
+        `recompute_maps` (extension, opt-in): the inversion stores no attention maps, only the latent every iteration was fed; each edit step
+        first re-runs the one inversion forward whose maps it reads (same kernels, same bytes: the edit is bit-identical to the resident
+        one) into a one-step slab, so the map arena is one step instead of one per DDIM step, at the price of an F-frame forward per edit
+        step.  Composes with every `map_dtype`; needs `use_inversion_attention=True`; with it `disk_store=True` has nothing to spill."""
         super().__init__(vae, text_encoder, tokenizer, unet, scheduler)
         self.map_dtype = self.default_map_dtype = map_dtype  # (default_map_dtype: what a YAML config without the key falls back to)
-        self.store_controller = attention_util.AttentionStore(disk_store=disk_store, map_dtype=map_dtype)
+        self.recompute_maps = self.default_recompute_maps = bool(recompute_maps)
+        self._source_tokens = None  # recompute_maps: the token-major input of the per-step source forward (one buffer, refilled every step)
+        self.store_controller = attention_util.AttentionStore(disk_store=disk_store, map_dtype=map_dtype, recompute=self.recompute_maps)
         self.empty_controller = attention_util.EmptyControl()
         # extension: a fatezero_amd.dist.FrameShard splits the clip's frames over the ranks of a process group; every rank
         # is handed (and returns) the full latents, keeps only its own frames' maps / masks in between
@@ -90,6 +97,49 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
             store = self.store_controller.with_map_dtype(map_dtype)  # (raises on an unknown name)
             self.release_attention_maps()
             self.store_controller, self.map_dtype = store, map_dtype
+
+    def set_recompute_maps(self, recompute_maps: bool):
+        """Switch the recompute mode (class docstring) for the jobs that follow: what the last inversion kept is dropped and a store of the
+        other mode takes the old one's place."""
+        if bool(recompute_maps) != self.recompute_maps:
+            store = self.store_controller.with_recompute(bool(recompute_maps))
+            self.release_attention_maps()
+            self.store_controller, self.recompute_maps = store, bool(recompute_maps)
+
+    def _refuse_issue_plans(self):
+        """recompute_maps and the native issue plans (fatezero_amd/issue.py) do not run together: on the MI355X a second editing prompt
+        replayed from plans beside the recomputed source forwards came out different from the walked job (the first one was bit-identical;
+        the cause is not found), so the combination is refused by name instead of being trusted."""
+        if getattr(self.unet, "_issuer", None) is not None or os.environ.get("FZ_ISSUE_PLANS") == "1":
+            raise RuntimeError("recompute_maps=True does not run under native issue plans (FZ_ISSUE_PLANS=1 / unet.enable_issue_plans()): "
+                               "switch one of the two off")
+
+    def _recompute_source_maps(self, controller, frames, h, w):
+        """recompute_maps, in front of an edit step: the inversion forward of the store step this edit step reads (attention and latent blend ask
+        for the same one: n - 1 - i), from that iteration's stored input latent, at its timestep, under the source context, one copy, with the
+        store controller registered as the inversion registers it -- into the store's step slab.  Ends behind the last captured map."""
+        store = controller.additional_attention_store
+        sis = controller._step_in_store()
+        if store.slab_step == sis:  # (the first edit after the inversion: its last iteration's maps are still in the slab)
+            return
+        latent, t, ctx = store.source_input(sis)
+        if tuple(latent.shape[-3:]) != (frames, h, w):
+            raise ValueError(f"recompute_maps: the inversion kept latents of {tuple(latent.shape[-3:])} (frames, h, w), the edit runs on "
+                             f"{(frames, h, w)}")
+        tok = self._source_tokens
+        if tok is None or tuple(tok.shape) != (frames, h * w, 4) or tok.device != latent.device:
+            tok = self._source_tokens = torch.empty(frames, h * w, 4, dtype=torch.float16, device=latent.device)
+        K.latent_tokens(latent[0].reshape(4, frames, h * w), out=tok)
+        low = store.LOW_RESOURCE
+        store.LOW_RESOURCE = True
+        attention_util.register_attention_control(self, store)
+        try:
+            store.begin_recompute(sis)
+            self.unet.forward_tokens(Tokens(tok, 1, frames, h, w), t, ctx, maps_up_to=attention_util.MAX_CONTROLLED_TOKENS)
+            store.end_recompute(sis)
+        finally:
+            store.LOW_RESOURCE = low
+            attention_util.register_attention_control(self, controller)
 
     def release_attention_maps(self):
         """Free the HBM map arena of the last inversion (and the edit controller that references it) so that the next
@@ -118,6 +168,11 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
                                       save_path=None, latents=None):
         """`latents` (extension): start from given clean latents [1,4,F,h,w] instead of VAE-encoding `image`."""
         self.prepare_before_train_loop()
+        # recompute_maps: the same inversion -- the store registered, the capturing launches, the running sum behind the cross-attention
+        # strips -- with every iteration's maps written over the previous one's; what the store keeps is each iteration's input latent
+        recompute = bool(store_attention and getattr(self.store_controller, "recompute", False))
+        if recompute:
+            self._refuse_issue_plans()
         if store_attention:
             attention_util.register_attention_control(self, self.store_controller)
         resource_default_value = self.store_controller.LOW_RESOURCE
@@ -141,7 +196,10 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
             latents = init.reshape(batch_size, bf // batch_size, c, h, w).permute(0, 2, 1, 3, 4)  # (b f) c h w -> b c f h w
         self.store_controller.expected_steps = len(self.scheduler.timesteps) if store_attention else None
         self.store_controller.latent_hw = tuple(latents.shape[-2:])  # the clip's own geometry: map sizes of every level follow from it
-        ddim_latents_all_step = self.ddim_clean2noisy_loop(latents, text_embeddings, self.store_controller)
+        if recompute:
+            ddim_latents_all_step = self.ddim_clean2noisy_loop(latents, text_embeddings, self.store_controller, keep_source=True)
+        else:
+            ddim_latents_all_step = self.ddim_clean2noisy_loop(latents, text_embeddings, self.store_controller)
         if store_attention and (save_path is not None):
             os.makedirs(save_path + "/cross_attention", exist_ok=True)
             attention_util.show_cross_attention(self.tokenizer, prompt, self.store_controller, 16, ["up", "down"],
@@ -151,7 +209,9 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         return ddim_latents_all_step
 
     @torch.no_grad()
-    def ddim_clean2noisy_loop(self, latent, text_embeddings, controller=None):
+    def ddim_clean2noisy_loop(self, latent, text_embeddings, controller=None, keep_source=False):
+        """`keep_source` (extension, recompute_maps): `controller` -- an AttentionStore(recompute=True) -- keeps what every iteration's
+        forward is fed (this rank's frames of `latent`, the source context, the timesteps; the later inputs are its `latents_store`)."""
         weight_dtype = latent.dtype
         uncond_embeddings, cond_embeddings = text_embeddings.chunk(2)
         shard = self.frame_shard
@@ -160,10 +220,14 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         all_latent = [latent]
         state = _LatentState(latent.detach(), reps=1)
         cond = cond_embeddings.to(torch.float16)
+        if keep_source:
+            controller.begin_source_pass(latent, cond)
         timesteps = self.scheduler.timesteps
         with fz_dist.frame_sharded(shard):
             for i in self.progress_bar(range(len(timesteps))):
                 t = int(timesteps[len(timesteps) - i - 1])
+                if keep_source:
+                    controller.source_timesteps.append(t)
                 eps = self.unet.forward_tokens(state.tokens(), t, cond)
                 cz, ce = self.scheduler.inverse_step_coefficients(t)
                 state.update(None, eps.data, 0.0, cz, ce)
@@ -233,6 +297,14 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
     def __call__(self, **kwargs):
         edit_type = kwargs["edit_type"]
         assert edit_type in ["save", "swap", None]
+        asked = kwargs.get("recompute_maps")  # per call / per p2p_config entry: may only repeat what the inversion ran with
+        if asked is not None and bool(asked) != self.recompute_maps:
+            raise ValueError(f"recompute_maps={bool(asked)} for this edit, but the pipeline (and its inversion) runs with "
+                             f"recompute_maps={self.recompute_maps}: what the inversion keeps decides the mode -- set it on the pipeline "
+                             "(constructor / set_recompute_maps / editing_config.recompute_attention_maps) before the inversion")
+        if self.recompute_maps and edit_type is not None and (edit_type == "save" or not kwargs.get("use_inversion_attention", False)):
+            raise ValueError("recompute_maps=True needs use_inversion_attention=True: with use_inversion_attention=False the stored maps come "
+                             "from an edit pass ('save', then 'swap'), there is no inversion forward to recompute them from")
         if edit_type is None:
             return self.sd_ddim_pipeline(controller=None, **kwargs)
         if edit_type == "save":
@@ -293,9 +365,15 @@ class P2pDDIMSpatioTemporalPipeline(SpatioTemporalStableDiffusionPipeline):
         state = _LatentState(latents.detach(), reps=2 if do_cfg else 1, share=shard is None)
         emb = text_embeddings.to(torch.float16)
         n_t = len(timesteps)
+        recompute = (isinstance(controller, attention_util.AttentionControlEdit) and controller.use_inversion_attention
+                     and getattr(controller.additional_attention_store, "recompute", False))
+        if recompute:
+            self._refuse_issue_plans()
         with fz_dist.frame_sharded(shard):
             for i, t in enumerate(self.progress_bar(timesteps)):
                 t = int(t)
+                if recompute:  # this step's stored maps: re-run the inversion forward they come from, into the one-step slab
+                    self._recompute_source_maps(controller, state.f, state.h, state.w)
                 eps = self.unet.forward_tokens(state.tokens(), t, emb).data
                 cz, ce = self.scheduler.step_coefficients(t)
                 if do_cfg:

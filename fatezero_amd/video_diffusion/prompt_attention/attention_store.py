@@ -483,13 +483,33 @@ def _views(cms):
     return list(cms) if any(cm.is_8bit for cm in cms) else [cm.view for cm in cms]
 
 
+class _StepSlab:
+    """The maps of ONE step, written again by every pass that captures into it (`AttentionStore(recompute=True)`): the first pass allocates
+    them in capture order, every later pass is handed the same CapturedMap objects by position -- the kernels' pointers never change."""
+    __slots__ = ("maps", "pos", "complete")
+
+    def __init__(self):
+        self.maps = {k: [] for k in KEYS}
+        self.pos = {k: 0 for k in KEYS}
+        self.complete = False
+
+    def rewind(self):
+        self.pos = {k: 0 for k in KEYS}
+
+
 class AttentionStore(AttentionControl):
     def __init__(self, save_self_attention: bool = True, disk_store=False, accumulate_self: bool = False, hbm_budget_bytes=None,
-                 map_dtype: str = "fp16"):
+                 map_dtype: str = "fp16", recompute: bool = False):
         super().__init__()
         if map_dtype not in MAP_DTYPES:
             raise ValueError("map_dtype must be one of %s, got %r" % (", ".join(repr(m) for m in MAP_DTYPES), map_dtype))
         self.map_dtype = map_dtype  # "e5m2" / "ue4m4": self-attention maps at one byte per probability (cross maps stay fp16)
+        # recompute=True (opt-in, the pipeline's `recompute_maps`): the store keeps NO map of the inversion -- only what the inversion forward
+        # of every iteration was fed (the first input latent + `latents_store`, the source context, the timesteps) -- and holds one step's
+        # maps at a time in a slab that the pipeline refills with `begin_recompute` / source forward / `end_recompute` right before the edit
+        # step that reads it.  `maps_of_step(s)` serves that slab; `attention_store_all_step` keeps its length (one entry per inversion
+        # step) but only the entry of the step in the slab holds tensors.  With it `disk_store` spills nothing: there is one step to hold.
+        self.recompute = bool(recompute)
         # The reference's disk_store=True writes every step's maps to ./trash/attention_cache_*/NNN.pt and loads them back in the edit
         # (attention_store.py:103-108, attention_util.py:115-116).  Here it switches the arena's spill tier on: steps stay in HBM while they
         # fit (`hbm_budget_bytes`, or FZ_ARENA_HBM_GB, or 90 % of what the device has free), the rest goes to pinned host memory behind the
@@ -510,8 +530,17 @@ class AttentionStore(AttentionControl):
         self._step_maps = {k: [] for k in KEYS}       # CapturedMap objects of the current step
         self._all_step_maps: List[Dict[str, List[CapturedMap]]] = []
         self._sum_storage: Dict[str, List[torch.Tensor]] = {}
-        self.arena = MapArena(spill=bool(self.disk_store), hbm_budget=self.hbm_budget_bytes)
+        self.arena = MapArena(spill=bool(self.disk_store) and not self.recompute, hbm_budget=self.hbm_budget_bytes)
         self._fetched = (None, None)  # (step, its maps in the ring slab) of the latest spilled step handed out
+        self._reset_recompute_state()
+
+    def _reset_recompute_state(self):
+        self._slab = None            # recompute mode: the step slab (every controlled map of one step)
+        self._slab_step = None       # the store step whose maps it holds (None: none / being written)
+        self._writing = False        # a forward is capturing into it
+        self.source_latent = None   # [1, 4, F(local), h, w]: the input of inversion iteration 0 (iteration k > 0 reads latents_store[k - 1])
+        self.source_context = None   # [1, 77, D] fp16: the conditional embedding of the source prompt the inversion ran with
+        self.source_timesteps = []   # the timestep of every inversion iteration
 
     @staticmethod
     def get_empty_store():
@@ -525,12 +554,32 @@ class AttentionStore(AttentionControl):
     def _wants(self, is_cross, lq):
         return lq <= MAX_CONTROLLED_TOKENS and (is_cross or self.save_self_attention)
 
+    def _slab_slot(self, shape, lk, device, map8, key) -> CapturedMap:
+        """recompute mode: the next map of the step slab -- allocated by the first pass over the slab, the same object in every later one."""
+        if not self._writing:
+            self._open_slab()
+        slab = self._slab
+        pos = slab.pos[key]
+        slab.pos[key] = pos + 1
+        if slab.complete:
+            cm = slab.maps[key][pos] if pos < len(slab.maps[key]) else None
+            if cm is None or tuple(cm.storage.shape) != tuple(shape) or cm.is_8bit != map8 or cm.storage.device != torch.device(device):
+                raise RuntimeError(f"recompute_maps: {key}[{pos}] of this forward is {tuple(shape)}, the step slab holds "
+                                   f"{None if cm is None else tuple(cm.storage.shape)}: the clip geometry changed after the first captured step")
+            return cm
+        cm = CapturedMap(self.arena.alloc(shape, device, itemsize=1 if map8 else 2), lk, self.map_dtype if map8 else "fp16")
+        slab.maps[key].append(cm)
+        return cm
+
     def new_slot(self, key, frames, heads, lq, lk, is_cross, device) -> CapturedMap:
         width = K.CROSS_P_STRIDE if is_cross else lk
         self._device = device
         map8 = self.map_dtype != "fp16" and not is_cross
-        cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device, itemsize=1 if map8 else 2), lk,
-                         self.map_dtype if map8 else "fp16")
+        if self.recompute:
+            cm = self._slab_slot((frames, heads, lq, width), lk, device, map8, key)
+        else:
+            cm = CapturedMap(self.arena.alloc((frames, heads, lq, width), device, itemsize=1 if map8 else 2), lk,
+                             self.map_dtype if map8 else "fp16")
         self._step_maps[key].append(cm)
         if self.map_dtype != "fp16":
             if not isinstance(self.step_store, LazyStepMaps):
@@ -555,7 +604,10 @@ class AttentionStore(AttentionControl):
     def issue_signature(self):
         if type(self).plan_controlled is not AttentionStore.plan_controlled:
             return None  # a subclass that plans differently says so itself
-        return ("store", bool(self.LOW_RESOURCE), bool(self.save_self_attention), self.map_dtype)
+        sig = ("store", bool(self.LOW_RESOURCE), bool(self.save_self_attention), self.map_dtype)
+        if self.recompute:  # (every step is captured into ONE slab)
+            sig += ("recompute",)
+        return sig
 
     def forward(self, attn, is_cross: bool, place_in_unet: str):
         """Reference tensor protocol (attention_store.py:81-93): keep a copy of the map."""
@@ -571,7 +623,7 @@ class AttentionStore(AttentionControl):
                 cm.view.copy_(attn)
         return attn
 
-    def between_steps(self):
+    def _sum_step(self):
         # running sum (attention_store.py:95-101), fp32, cross maps (+ self maps on request)
         keys = [k for k in KEYS if k.endswith("cross") or self.accumulate_self]
         if len(self.attention_store) == 0:
@@ -586,6 +638,79 @@ class AttentionStore(AttentionControl):
             for k in keys:
                 for acc, cm in zip(self._sum_storage[k], self._step_maps[k]):
                     K.accumulate(acc, cm.half())
+
+    # -- recompute mode --------------------------------------------------------------------------------------
+    # The inversion of this mode IS the resident inversion -- the store registered, the capturing launches, the running sum of the cross maps
+    # (so `show_cross_attention` renders the same strips) -- except that every iteration captures into the same slab: a plain-flash inversion
+    # would not do, its attention outputs differ from the capturing launches' in the last bits and the edit could not reproduce a resident job.
+    def begin_source_pass(self, latent, context):
+        """In front of the inversion loop: keep what iteration 0 is fed (`latent` [1, 4, F, h, w], this rank's frames) and the source
+        context; the later inputs are `latents_store`, the timesteps are appended by the loop."""
+        if self.latents_store or self._all_step_maps:
+            self.reset()  # an earlier inversion's latents: the step indices of this one start at 0
+        self.source_latent = latent.detach().clone(memory_format=torch.contiguous_format)  # (a VAE-encoded clip arrives as a permuted view)
+        self.source_context = context.detach().to(torch.float16).clone()
+        self.source_timesteps = []
+
+    @property
+    def slab_step(self):
+        """The store step whose maps are resident (None: none)."""
+        return self._slab_step
+
+    def _open_slab(self):
+        if self._slab is None:
+            self._slab = _StepSlab()
+        if self._slab_step is not None:
+            self.attention_store_all_step[self._slab_step] = self.get_empty_store()  # (its views would show the step that overwrites them)
+        self._slab_step = None
+        self._slab.rewind()
+        self._writing = True
+
+    def _close_slab(self, step_in_store):
+        slab = self._slab
+        if self._writing:
+            if slab.complete and any(slab.pos[k] != len(slab.maps[k]) for k in KEYS):
+                raise RuntimeError("recompute_maps: this forward captured fewer maps than the step slab holds")
+            slab.complete = True
+            self._writing = False
+            self._slab_step = step_in_store
+            self.attention_store_all_step[step_in_store] = self.step_store
+        self.step_store = self.get_empty_store()
+        self._step_maps = {k: [] for k in KEYS}
+
+    def source_input(self, step_in_store):
+        """(input latent [1, 4, F, h, w], timestep, context) of inversion iteration `step_in_store`."""
+        lat = self.source_latent if step_in_store == 0 else self.latents_store[step_in_store - 1]
+        return lat, self.source_timesteps[step_in_store], self.source_context
+
+    def begin_recompute(self, step_in_store):
+        """The source forward that follows (this store registered, LOW_RESOURCE) writes the maps of inversion iteration `step_in_store` into
+        the step slab."""
+        if not self.recompute or self.source_latent is None:
+            raise RuntimeError("begin_recompute needs AttentionStore(recompute=True) after an inversion in that mode")
+        self.cur_att_layer = 0
+        self.step_store = self.get_empty_store()
+        self._step_maps = {k: [] for k in KEYS}
+        self._open_slab()
+
+    def end_recompute(self, step_in_store):
+        self._close_slab(step_in_store)
+        self.cur_att_layer = 0
+
+    def _between_steps_recompute(self):
+        """An inversion step in recompute mode: the running sum as ever, then the step's maps stay where they are -- in the slab the next
+        iteration overwrites.  The per-step lists get an entry all the same: their length is what the edit controller counts its way back
+        from (`_step_in_store`)."""
+        self._sum_step()
+        step = len(self._all_step_maps)
+        self.attention_store_all_step.append(self.get_empty_store())
+        self._all_step_maps.append(None)
+        self._close_slab(step)
+
+    def between_steps(self):
+        if self.recompute:
+            return self._between_steps_recompute()
+        self._sum_step()
         self.attention_store_all_step.append(self.step_store)
         self._all_step_maps.append(self._step_maps)
         self.step_store = self.get_empty_store()
@@ -633,13 +758,26 @@ class AttentionStore(AttentionControl):
     def with_map_dtype(self, map_dtype: str):
         """A fresh store of this one's settings with another map format (this one's maps are not carried over)."""
         st = AttentionStore(save_self_attention=self.save_self_attention, disk_store=self.disk_store, accumulate_self=self.accumulate_self,
-                            hbm_budget_bytes=self.hbm_budget_bytes, map_dtype=map_dtype)
+                            hbm_budget_bytes=self.hbm_budget_bytes, map_dtype=map_dtype, recompute=self.recompute)
+        st.LOW_RESOURCE = self.LOW_RESOURCE
+        return st
+
+    def with_recompute(self, recompute: bool):
+        """A fresh store of this one's settings with the recompute mode switched (this one's maps are not carried over)."""
+        st = AttentionStore(save_self_attention=self.save_self_attention, disk_store=self.disk_store, accumulate_self=self.accumulate_self,
+                            hbm_budget_bytes=self.hbm_budget_bytes, map_dtype=self.map_dtype, recompute=recompute)
         st.LOW_RESOURCE = self.LOW_RESOURCE
         return st
 
     def maps_of_step(self, step_in_store) -> Dict[str, List[CapturedMap]]:
         if step_in_store < 0:
             step_in_store += len(self._all_step_maps)
+        if self.recompute:
+            if self._slab_step != step_in_store:
+                raise RuntimeError(f"recompute_maps: the maps of store step {step_in_store} are not resident (the step slab holds "
+                                   f"{'no step' if self._slab_step is None else 'step %d' % self._slab_step}): the pipeline recomputes a "
+                                   "step right before the edit step that reads it")
+            return self._slab.maps
         maps = self._all_step_maps[step_in_store]
         if maps is not None:
             return maps
@@ -675,6 +813,7 @@ class AttentionStore(AttentionControl):
             # invalid from here on; a store that is used again reserves a fresh arena instead of allocating per step
             self.arena = type(arena)(spill=arena.spill, hbm_budget=arena.hbm_budget)
             self._fetched = (None, None)
+            self._reset_recompute_state()
 
     def __del__(self):
         try:

@@ -123,9 +123,12 @@ class AttentionControlEdit(AttentionStore, abc.ABC):
         if type(self).plan_controlled is not AttentionControlEdit.plan_controlled:
             return None
         in_self_window = self.num_self_replace[0] <= self.cur_step < self.num_self_replace[1]
-        return ("edit", bool(self.LOW_RESOURCE), bool(self.save_self_attention), bool(in_self_window), self.attention_blend is not None,
-                bool(self.track_cross_attention), self.visualize_res, self.map_dtype,
-                getattr(self.additional_attention_store, "map_dtype", "fp16"))
+        sig = ("edit", bool(self.LOW_RESOURCE), bool(self.save_self_attention), bool(in_self_window), self.attention_blend is not None,
+               bool(self.track_cross_attention), self.visualize_res, self.map_dtype,
+               getattr(self.additional_attention_store, "map_dtype", "fp16"))
+        if getattr(self.additional_attention_store, "recompute", False):  # (the stored maps are ONE slab, rewritten between the edit steps)
+            sig += ("recompute",)
+        return sig
 
     def _is_visualize_level(self, lq):
         """The level `show_cross_attention(..., visualize_res, ...)` renders: the one whose longer side is `visualize_res`."""

@@ -428,6 +428,14 @@ int fz_transpose_pad(const void* in, void* out, int n, int l, int c, int64_t in_
 int fz_latent_update(float* z, const void* eps_u, const void* eps_c, float guidance, float cz, float ce,
                      const float* inv, const float* mask, void* next_in, int frames, int hw, void* stream);
 
+/* A stored latent as the UNet input: tok[f][pix][c] = (fp16, round to nearest even) z[c][f][pix], z: [4][F][hw] of z_dtype
+ * (FZ_LATENT_F32 | FZ_LATENT_F16), tok: fp16 token-major [F][hw][4], 8-byte aligned, one 8-byte store per token, 64-bit indexing.
+ * The per-step source forward of the pipeline's recompute_maps mode starts from it.  FZ_ERR_BAD_ARG: a null / misaligned / aliased
+ * pointer, frames <= 0, hw <= 0, another z_dtype. */
+#define FZ_LATENT_F32 0
+#define FZ_LATENT_F16 1
+int fz_latent_tokens(const void* z, int z_dtype, void* tok, int frames, int hw, void* stream);
+
 /* fp16 running-sum helper for the edit controller's accumulated cross maps (attention_store.py:95-101):
  * acc (float) += x (fp16), n elements. */
 int fz_accumulate(float* acc, const void* x, int64_t n, void* stream);
