@@ -14,7 +14,7 @@ HIP_LIB = os.path.join(HERE, "libfatezero_hip.so")
 FZ_ATTN_FLASH, FZ_ATTN_CAPTURE, FZ_ATTN_INJECT = 0, 1, 2
 FZ_ATTN_CAPTURE8, FZ_ATTN_INJECT8 = 3, 4  # fz_attn_self: the map as E5M2 bytes (strides in bytes)
 FZ_ATTN_CAPTURE8U, FZ_ATTN_INJECT8U = 5, 6  # fz_attn_self: the map as UE4M4 bytes (bits 13..6 of each fp16 probability)
-FZ_MAX_KV_SLOTS = 4
+FZ_MAX_KV_SLOTS = 8  # entries of a SparseCausalAttention_index list (include/fatezero_hip.h)
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80
 FZ_TEMPORAL_MAX_FRAMES = 512

@@ -19,6 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from . import config_driver
+from . import kernels
 from .video_diffusion.common.image_util import log_train_samples
 from .video_diffusion.common.instantiate_from_config import instantiate_from_config
 from .video_diffusion.data.dataset import ImageSequenceDataset
@@ -94,6 +95,8 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
         set_seed(seed)
     device = torch.device(device if device is not None else ("cuda:0" if torch.cuda.is_available() else "cpu"))
 
+    # (a list the kernels cannot serve is named here, before any checkpoint file is read; the model's constructor checks it again)
+    kernels.check_kv_slot_count((model_config or {}).get("SparseCausalAttention_index", []))
     tokenizer = CLIPTokenizer.from_pretrained(pretrained_model_path, subfolder="tokenizer")
     text_encoder = CLIPTextModel.from_pretrained(pretrained_model_path, subfolder="text_encoder")
     vae = AutoencoderKL.from_pretrained(pretrained_model_path, subfolder="vae")

@@ -140,13 +140,14 @@ attn_flash_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* 
                            : fz_zero_h8();
         }
     }
-    // source frames of the kv slots (wave-uniform scalars); when ALL slots resolve to one frame the keys are read once
-    int src[FZ_MAX_KV_SLOTS];
+    // Source frames of the kv slots: wave-uniform, and needed only where a slot begins (once every tps tiles), so none is kept --
+    // fetch() derives the one it needs from the descriptor in the kernel arguments (scalar arithmetic on a scalar slot index).  A
+    // per-thread array of FZ_MAX_KV_SLOTS sources indexed by the run-time slot would be a candidate for scratch at eight entries.
+    // When ALL slots resolve to one frame the keys are read once.
     bool one_source = true;
-#pragma unroll
-    for (int j = 0; j < FZ_MAX_KV_SLOTS; ++j) {
-        src[j] = fl_kv_source(d, b, f, j);
-        one_source = one_source && (j >= d.n_kv || src[j] == src[0]);
+    {
+        const int src0 = fl_kv_source(d, b, f, 0);
+        for (int j = 1; j < d.n_kv; ++j) one_source = one_source && fl_kv_source(d, b, f, j) == src0;
     }
     const int nkv = one_source ? 1 : d.n_kv;
     const int lkfp = (d.lkf + FKVBLK - 1) / FKVBLK * FKVBLK;
@@ -212,8 +213,9 @@ attn_flash_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* 
     const char *kcur = nullptr, *vcur = nullptr;
     auto fetch = [&]() {
         if (fr0 == 0) {  // wave-uniform: first tile of a kv slot
-            kcur = reinterpret_cast<const char*>(k + (int64_t)src[fj] * d.k_frame_stride + (int64_t)h * khs);
-            vcur = reinterpret_cast<const char*>(vt + (int64_t)src[fj] * d.vt_frame_stride + (int64_t)(h * D) * d.vt_chan_stride);
+            const int src = fl_kv_source(d, b, f, fj);
+            kcur = reinterpret_cast<const char*>(k + (int64_t)src * d.k_frame_stride + (int64_t)h * khs);
+            vcur = reinterpret_cast<const char*>(vt + (int64_t)src * d.vt_frame_stride + (int64_t)(h * D) * d.vt_chan_stride);
         }
         const uint32_t kmax = (uint32_t)(d.lkf - 1 - fr0);  // padded keys are masked / neutralised; any finite data will do
 #pragma unroll

@@ -168,14 +168,19 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
                     : fz_zero_h8();
     }
 
-    int src[FZ_MAX_KV_SLOTS];
+    // Source frames of the kv slots: wave-uniform.  A per-thread table of FZ_MAX_KV_SLOTS ints indexed by the run-time slot would be a
+    // candidate for scratch at eight entries, so the clip-relative source frames (< 2^16, checked by the launcher) are packed four to a
+    // 64-bit scalar; fetch() takes the one of its slot out with a shift -- scalar arithmetic on the scalar slot index.
+    const int kvl = d.kv_clip_len ? d.kv_clip_len : d.clip_len;  // frames per batch element of k / vt
+    static_assert(FZ_MAX_KV_SLOTS == 8, "two 64-bit scalars of four 16-bit source frames");
+    uint64_t srcs_lo = 0, srcs_hi = 0;  // slots 0..3, slots 4..7
 #pragma unroll
     for (int j = 0; j < FZ_MAX_KV_SLOTS; ++j) {
-        const int kvl = d.kv_clip_len ? d.kv_clip_len : d.clip_len;  // frames per batch element of k / vt
         int s = d.kv_abs[j] ? d.kv_val[j] : f + (d.kv_clip_len ? d.kv_frame_off : 0) + d.kv_val[j];
         s = s < 0 ? 0 : (s > kvl - 1 ? kvl - 1 : s);
-        src[j] = b * kvl + s;
+        (j < 4 ? srcs_lo : srcs_hi) |= (uint64_t)(uint32_t)s << (16 * (j & 3));
     }
+    auto kv_source = [&](int j) { return b * kvl + (int)(((j & 4) ? srcs_hi : srcs_lo) >> (16 * (j & 3)) & 0xFFFFu); };
 
     const int lkfp = (d.lkf + KVBLK - 1) / KVBLK * KVBLK;
     const int tps = lkfp / KVBLK;
@@ -241,8 +246,9 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
     }
     auto fetch = [&](int kt, bool with_k, bool with_v) {
         const int j = kt / tps, r0 = (kt % tps) * KVBLK;
+        const int src = kv_source(j);
         if (with_k) {
-            const char* kb = reinterpret_cast<const char*>(k + (int64_t)src[j] * d.k_frame_stride + (int64_t)h * khs) +
+            const char* kb = reinterpret_cast<const char*>(k + (int64_t)src * d.k_frame_stride + (int64_t)h * khs) +
                              (int64_t)r0 * krs_bytes;
             const uint32_t kmax = (uint32_t)(d.lkf - 1 - r0);  // padded keys are masked in the softmax; any finite data will do
 #pragma unroll
@@ -252,7 +258,7 @@ attn_self_kernel(FzAttnSelfDesc d, const half_t* __restrict__ q, const half_t* _
             }
         }
         if (with_v) {
-            const char* vb = reinterpret_cast<const char*>(vt + (int64_t)src[j] * d.vt_frame_stride +
+            const char* vb = reinterpret_cast<const char*>(vt + (int64_t)src * d.vt_frame_stride +
                                                            (int64_t)(h * D) * d.vt_chan_stride + r0);
 #pragma unroll
             for (int i = 0; i < C::VLD; ++i) vreg[i] = fz_ld_h8_off(vb, voff[i]);
@@ -668,6 +674,8 @@ extern "C" int fz_attn_self(const FzAttnSelfDesc* desc, const void* q, const voi
     const FzAttnSelfDesc& d = *desc;
     if (d.n_frames <= 0 || d.lq <= 0 || d.lkf <= 0 || d.n_kv < 1 || d.n_kv > FZ_MAX_KV_SLOTS) return FZ_ERR_BAD_ARG;
     if (d.mode != FZ_ATTN_FLASH && !p) return FZ_ERR_BAD_ARG;
+    if (d.mode != FZ_ATTN_FLASH && (d.kv_clip_len ? d.kv_clip_len : d.clip_len) > (1 << 16))
+        return FZ_ERR_UNSUPPORTED;  // attn_self_kernel packs clip-relative source frames into 16 bits
     const bool inject = d.mode == FZ_ATTN_INJECT || d.mode == FZ_ATTN_INJECT8 || d.mode == FZ_ATTN_INJECT8U;
     if (!(inject && row_mask == nullptr) && !k) return FZ_ERR_BAD_ARG;
     if ((d.q_row_stride | d.k_row_stride | d.vt_chan_stride | d.o_row_stride | d.q_frame_stride | d.k_frame_stride |

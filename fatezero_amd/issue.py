@@ -286,6 +286,7 @@ class IssuePlans:
         self.seen = {}
         self.plans = {}
         self._probe = None
+        self._sc_blocks = None
         self.stats = {"walked": 0, "recorded": 0, "replayed": 0, "contexts_bound": 0, "unsupported": 0, "unrecordable": []}
 
     # -- what kind of forward is this ----------------------------------------------------------------------
@@ -294,6 +295,14 @@ class IssuePlans:
             from .video_diffusion.models.attention import CrossAttention
             self._probe = next(m for m in self.unet.modules() if isinstance(m, CrossAttention))
         return self._probe.controller
+
+    def _sc_lists(self):
+        """The SparseCausalAttention_index of every transformer block, as the blocks read it at this forward (model_config is a plain dict):
+        the list's length is n_kv of the recorded self-attention launches and the width of the maps they store."""
+        if self._sc_blocks is None:
+            from .video_diffusion.models.attention import SpatioTemporalTransformerBlock
+            self._sc_blocks = [m for m in self.unet.modules() if isinstance(m, SpatioTemporalTransformerBlock)]
+        return tuple(tuple(b.sc_index) for b in self._sc_blocks)
 
     def clear(self):
         self.seen.clear()
@@ -312,7 +321,8 @@ class IssuePlans:
                 return None
         return (tuple(x.data.shape), x.b, x.rep, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
                 ctx.dtype, type(controller), sig, _model_switches(),  # (sig carries the map format)
-                getattr(self.unet, "_maps_up_to", None))  # (a forward that ends behind its last captured map is another launch list)
+                getattr(self.unet, "_maps_up_to", None),  # (a forward that ends behind its last captured map is another launch list)
+                self._sc_lists())  # (another index list is another n_kv in every self-attention record)
 
     # -- record --------------------------------------------------------------------------------------------
     @classmethod

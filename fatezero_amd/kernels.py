@@ -19,6 +19,7 @@ MAP8_FORMATS = ("e5m2", "ue4m4")  # what a torch.uint8 map may hold: the tensor 
 CROSS_P_STRIDE = N.FZ_CROSS_P_STRIDE
 CROSS_KEYS = N.FZ_CROSS_MAX_KEYS
 TEMPORAL_MAX_FRAMES = N.FZ_TEMPORAL_MAX_FRAMES
+MAX_KV_SLOTS = N.FZ_MAX_KV_SLOTS
 SUPPORTED_HEAD_DIMS = (16, 32, 40, 64, 80, 128, 160)
 
 
@@ -103,11 +104,20 @@ def self_mode_for(mode: int, p: Optional[torch.Tensor], map8_format: str = "e5m2
 # ------------------------------------------------------------------------------------------------------------
 # sparse-causal self attention
 # ------------------------------------------------------------------------------------------------------------
+def check_kv_slot_count(index_list: Sequence) -> None:
+    """A SparseCausalAttention_index list may name up to MAX_KV_SLOTS frames: FzAttnSelfDesc carries that many kv slots."""
+    if len(index_list) > MAX_KV_SLOTS:
+        raise ValueError("SparseCausalAttention_index may have up to %d entries (FZ_MAX_KV_SLOTS = %d); got %d: %r"
+                         % (MAX_KV_SLOTS, MAX_KV_SLOTS, len(index_list), list(index_list)))
+
+
 def kv_slots(index_list: Sequence, clip_len: int) -> Tuple[List[int], List[int]]:
     """SparseCausalAttention_index -> per kv slot (is_absolute, frame or offset), attention_register.py:162-183.
-    An empty list means 'own frame' (attention.py:171-173 sets it for dim < least_sc_channel)."""
+    An empty list means 'own frame' (attention.py:171-173 sets it for dim < least_sc_channel).  More than MAX_KV_SLOTS entries are a
+    ValueError that names the limit."""
     if len(index_list) == 0:
         return [0], [0]
+    check_kv_slot_count(index_list)
     kabs, kval = [], []
     for index in index_list:
         if isinstance(index, str):
@@ -167,6 +177,7 @@ def attn_self(q: torch.Tensor, k: Optional[torch.Tensor], vt: torch.Tensor, out:
         _chk16(q, k, vt, out, p)
     n_frames = N_ - frame0 if n_frames is None else n_frames
     kabs, kval = kv_slots(index_list, clip_len) if kv_slots_override is None else kv_slots_override
+    check_kv_slot_count(index_list if kv_slots_override is None else kabs)
     d = N.FzAttnSelfDesc()
     d.kv_clip_len, d.kv_frame_off = kv_clip_len, kv_frame_off
     d.n_frames, d.frame0, d.clip_len, d.heads, d.head_dim = n_frames, frame0, clip_len, heads, d_head

@@ -496,6 +496,7 @@ class SpatioTemporalTransformerBlock(nn.Module):
         self.model_config = copy.deepcopy(model_config)
         if "least_sc_channel" in model_config and dim < model_config["least_sc_channel"]:
             self.model_config["SparseCausalAttention_index"] = []  # attention.py:171-173
+        K.check_kv_slot_count(self.sc_index)  # a list the kernels cannot serve fails here, before any checkpoint is read
         self.attn1 = SparseCausalAttention(query_dim=dim, heads=num_attention_heads, dim_head=attention_head_dim)
         self.norm1 = _NormParams(dim)
         self.attn2 = CrossAttention(query_dim=dim, cross_attention_dim=cross_attention_dim, heads=num_attention_heads,

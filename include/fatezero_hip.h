@@ -40,7 +40,9 @@ extern "C" {
 #define FZ_ATTN_CAPTURE8U 5
 #define FZ_ATTN_INJECT8U 6
 
-#define FZ_MAX_KV_SLOTS 4
+/* Entries a SparseCausalAttention_index list may have.  It was 4 before; with 8, FzAttnSelfDesc grew by 32 bytes (kv_abs and kv_val
+ * hold 8 entries each, every later member moved), so out-of-tree binders of the struct must rebuild against this header. */
+#define FZ_MAX_KV_SLOTS 8
 
 /* Sparse-causal spatio-temporal self-attention: `spatial_temporal_forward` + `_attention`
  * (attention_register.py:131-218, :23-59; SparseCausalAttention.forward attention.py:340-422), with the
@@ -58,7 +60,7 @@ typedef struct FzAttnSelfDesc {
     int32_t head_dim;   /* 16, 32, 40, 64, 80, 128 or 160                                    */
     int32_t lq;         /* query tokens per frame                                            */
     int32_t lkf;        /* key tokens per kv slot (= tokens per source frame)                */
-    int32_t n_kv;       /* 1..FZ_MAX_KV_SLOTS                                                */
+    int32_t n_kv;       /* 1..FZ_MAX_KV_SLOTS (8); anything else is FZ_ERR_BAD_ARG           */
     int32_t kv_abs[FZ_MAX_KV_SLOTS];
     int32_t kv_val[FZ_MAX_KV_SLOTS];
     float scale;        /* head_dim^-0.5                                                     */
@@ -81,7 +83,8 @@ typedef struct FzAttnSelfDesc {
      * frames [left halo | the rank's own frames | right halo | anchor frames] gathered from their owners, while q / o
      * keep clip_len (= local) frames.  A relative slot reads frame clamp(f + kv_frame_off + kv_val, 0, kv_clip_len-1),
      * an absolute slot reads frame kv_val of that extended axis.  kv_clip_len == 0: k / vt have clip_len frames and
-     * kv_frame_off is ignored (the single-GPU layout). */
+     * kv_frame_off is ignored (the single-GPU layout).  The capture / inject modes carry a slot's source frame inside its batch
+     * element in 16 bits: more than 65536 frames per batch element of k / vt is FZ_ERR_UNSUPPORTED there. */
     int32_t kv_clip_len;
     int32_t kv_frame_off;
     int32_t reserved0;
