@@ -18,6 +18,7 @@ FZ_MAX_KV_SLOTS = 8  # entries of a SparseCausalAttention_index list (include/fa
 FZ_CROSS_MAX_KEYS = 96
 FZ_CROSS_P_STRIDE = 80
 FZ_TEMPORAL_MAX_FRAMES = 512
+FZ_TEMPORAL_MAX_WINDOW = 96  # largest temporal_attention_window on clips of more than 64 frames (include/fatezero_hip.h)
 FZ_LATENT_F32, FZ_LATENT_F16 = 0, 1  # fz_latent_tokens: element type of the stored latent
 FZ_ERR_BAD_ARG = -1
 
@@ -109,6 +110,8 @@ _SIGS = {
                                    C.c_int64, C.c_float, _P]),
     "fz_attn_temporal_ex": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       C.c_int64, C.c_int64, C.c_float, _P]),
+    "fz_attn_temporal_win": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_float, _P]),
     "fz_blend_mask": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, _P,
                                 C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "fz_blend_mask_hw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P,

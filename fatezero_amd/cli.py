@@ -97,6 +97,7 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
 
     # (a list the kernels cannot serve is named here, before any checkpoint file is read; the model's constructor checks it again)
     kernels.check_kv_slot_count((model_config or {}).get("SparseCausalAttention_index", []))
+    config_driver.temporal_window_of(model_config)
     tokenizer = CLIPTokenizer.from_pretrained(pretrained_model_path, subfolder="tokenizer")
     text_encoder = CLIPTextModel.from_pretrained(pretrained_model_path, subfolder="text_encoder")
     vae = AutoencoderKL.from_pretrained(pretrained_model_path, subfolder="vae")
@@ -153,11 +154,16 @@ def test(config: str, pretrained_model_path: str, dataset_config: Dict, logdir: 
     return {"logdir": logdir, "samples": samples, "latents_all_step": latents_all_step}
 
 
-def run_config_file(config: str, image_size=None, **overrides):
+def run_config_file(config: str, image_size=None, temporal_window=None, **overrides):
     """test_fatezero.py:254-276: one run for a checkpoint folder that holds `unet/`, otherwise one per `checkpoint_*` child.
-    `image_size` (an int or a (height, width) pair) replaces `dataset_config.image_size`."""
+    `image_size` (an int or a (height, width) pair) replaces `dataset_config.image_size`, `temporal_window` (an int)
+    `model_config.temporal_attention_window`."""
     cfg = config_driver.load_config(config)
     cfg.update(overrides)
+    if temporal_window is not None:
+        mc = dict(cfg.get("model_config") or {})
+        mc["temporal_attention_window"] = config_driver.temporal_window_of(mc, temporal_window)
+        cfg["model_config"] = mc
     if image_size is not None and tuple(image_size) != ():
         cfg["dataset_config"] = dict(cfg["dataset_config"], image_size=config_driver.image_size_of({"image_size": image_size}))
     root = cfg["pretrained_model_path"]
@@ -188,11 +194,14 @@ def run():
     @click.option("--recompute-maps/--no-recompute-maps", default=None,
                   help="keep the inversion's latents instead of its attention maps and recompute each step's maps during the edit "
                        "(default: editing_config.recompute_attention_maps, else off)")
-    def _main(config, map_dtype, image_size, recompute_maps):
+    @click.option("--temporal-window", type=int, default=None, metavar="W",
+                  help="temporal attention: every frame attends the frames within W of it instead of the whole clip "
+                       "(default: model_config.temporal_attention_window, else the whole clip)")
+    def _main(config, map_dtype, image_size, recompute_maps, temporal_window):
         over = {} if map_dtype is None else {"map_dtype": map_dtype}
         if recompute_maps is not None:
             over["recompute_maps"] = recompute_maps
-        run_config_file(config, image_size=image_size, **over)
+        run_config_file(config, image_size=image_size, temporal_window=temporal_window, **over)
 
     _main()
 

@@ -117,6 +117,16 @@ def recompute_maps_of(editing_config: Optional[Dict[str, Any]], override: Option
     return value
 
 
+def temporal_window_of(model_config: Optional[Dict[str, Any]], override: Optional[int] = None) -> Optional[int]:
+    """Temporal attention's window: `override` (the --temporal-window switch), else the optional `model_config.temporal_attention_window`
+    key (an extension: no reference config has it), else None -- every frame of the clip.  W: a query frame attends the frames within W
+    of it.  A value that is neither None nor a non-negative int is a ValueError."""
+    from . import kernels
+    value = override if override is not None else (model_config or {}).get("temporal_attention_window")
+    kernels.check_temporal_window(value)
+    return value
+
+
 def image_size_of(dataset_config: Optional[Dict[str, Any]]):
     """`dataset_config.image_size`: an int (square frames, the reference's form) or a `[height, width]` pair (an extension: a clip edited at
     its own aspect ratio).  Returns the int, or the pair as a tuple of ints; 512 when the key is absent (the dataset's default)."""

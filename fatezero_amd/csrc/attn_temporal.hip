@@ -665,3 +665,292 @@ extern "C" int fz_attn_temporal(const void* q, const void* k, const void* v, voi
     return fz_attn_temporal_ex(q, k, v, o, batch, clip_len, clip_len, tokens, heads, head_dim, qkv_row_stride,
                                qkv_row_stride, o_row_stride, scale, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Windowed temporal attention (fz_attn_temporal_win): query frame f -- an ABSOLUTE index among the kv_frames, q_frame0 + its row --
+// attends the key/value frames j with |j - f| <= W, cut at the clip's ends (nothing is padded: frame 0 attends W + 1 frames).  The
+// numeric contract is the one of every kernel above: scores in fp32, the exact softmax over the attended keys, P normalised, THEN
+// rounded to fp16, O accumulated in fp32 and rounded once.  A window that covers the clip (W >= kv_frames - 1) never gets here: the
+// entry point hands it to fz_attn_temporal_ex.  Nothing above this line is touched by the windowed form.
+//
+// Up to TMAXF key/value frames: attn_temporal_kernel with loop bounds -- one thread per (token, head, query frame), the at most
+// 2 W + 1 scores of its band in LDS.
+struct TemporalWinArgs {
+    const half_t *q, *k, *v;
+    half_t* o;
+    int batch, F, Fq, q0, W, ns, tokens, heads, dh;  // ns: score slots per thread, min(2 W + 1, F)
+    int64_t in_stride, q_stride, out_stride;
+    float scale;
+    int tok_per_block;
+};
+
+FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_win_kernel(TemporalWinArgs a) {
+    FZ_DYN_SMEM(raw);
+    float* S = reinterpret_cast<float*>(raw);  // [TTHREADS][ns]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y;
+    const int tok0 = blockIdx.x * a.tok_per_block;
+    const int items = a.tok_per_block * a.heads * a.Fq;
+    const int nvec = a.dh >> 3;
+    float* myS = S + tid * a.ns;
+    for (int w = tid; w < items; w += TTHREADS) {
+        const int h = w % a.heads;
+        const int tl = (w / a.heads) % a.tok_per_block;
+        const int i = w / (a.heads * a.tok_per_block);
+        const int tok = tok0 + tl;
+        if (tok >= a.tokens) continue;
+        const int f = a.q0 + i;  // absolute frame of this query
+        const int j0 = f - a.W > 0 ? f - a.W : 0;
+        const int j1 = f + a.W < a.F - 1 ? f + a.W : a.F - 1;  // the band [j0, j1]: never empty (q0 + Fq <= F), at most ns frames
+        const int64_t col = (int64_t)h * a.dh;
+        const half_t* qrow = a.q + ((int64_t)(b * a.Fq + i) * a.tokens + tok) * a.q_stride + col;
+        float mx = -1e30f;
+        for (int j = j0; j <= j1; ++j) {
+            const half_t* krow = a.k + ((int64_t)(b * a.F + j) * a.tokens + tok) * a.in_stride + col;
+            float acc = 0.0f;
+            for (int c = 0; c < nvec; ++c) {
+                const half8_t qv = fz_ld_h8(qrow + 8 * c), kv = fz_ld_h8(krow + 8 * c);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc += (float)qv[e] * (float)kv[e];
+            }
+            acc *= a.scale;
+            myS[j - j0] = acc;
+            mx = fmaxf(mx, acc);
+        }
+        float sum = 0.0f;
+        for (int j = j0; j <= j1; ++j) {
+            const float e = __builtin_expf(myS[j - j0] - mx);
+            myS[j - j0] = e;
+            sum += e;
+        }
+        const float inv = 1.0f / sum;
+        for (int j = j0; j <= j1; ++j) myS[j - j0] = (float)(half_t)(myS[j - j0] * inv);  // P is cast to fp16 before P.V
+        half_t* orow = a.o + ((int64_t)(b * a.Fq + i) * a.tokens + tok) * a.out_stride + col;
+        for (int c = 0; c < nvec; ++c) {
+            float acc[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+            for (int j = j0; j <= j1; ++j) {
+                const half8_t vv = fz_ld_h8(a.v + ((int64_t)(b * a.F + j) * a.tokens + tok) * a.in_stride + col + 8 * c);
+                const float pj = myS[j - j0];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += pj * (float)vv[e];
+            }
+            half8_t ov;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ov[e] = (half_t)acc[e];
+            fz_st_h8(orow + 8 * c, ov);
+        }
+    }
+}
+
+// Beyond TMAXF key/value frames: the band kernel.  The two transposed MFMA products of attn_temporal_long_kernel (S^T = K Q^T with
+// whole score rows in registers, the exact two-pass softmax, O^T = V^T P^T with P^T the C fragment as it lies), but a 32-query tile
+// contracts only the key tiles that overlap its band:
+//   tile arithmetic   the wave's queries are the absolute frames a0 .. a0 + 31 (a0 = q_frame0 + 32 qt), their keys lie in
+//                     [a0 - W, a0 + 31 + W] cut at the clip's ends.  Key tiles are ALIGNED TO ABSOLUTE MULTIPLES OF 32 FRAMES (first tile
+//                     t0 = max(a0 - W, 0) / 32), so a key always sits in the same fragment slot whatever q_frame0 and whichever other
+//                     queries share the launch; a span of 32 + 2 W frames touches at most NT = ceil((32 + 2 W) / 32) + 1 aligned tiles:
+//                     2 at W = 0, 3 up to W = 16, 8 at W = 96 = FZ_TEMPORAL_MAX_WINDOW (the 8 x 16 fp32 score registers
+//                     attn_temporal_long_kernel<8> holds without scratch).  Tiles of the NT that lie wholly beyond the band or the clip are
+//                     skipped (wave-uniform).
+//   mask              key j counts for query f iff |j - f| <= W and j < F; every other score is -1e30 before the softmax and its P is
+//                     exactly 0.  The sum over a row runs in a FIXED order with re-association off: masked slots add an exact 0, so a
+//                     query's l -- and with it every bit of its output -- does not depend on where its tile's first key tile lies.  That
+//                     is what makes a frame-sharded launch bit-equal to the same rows of the whole-clip launch.
+//   V                 is never staged for the clip, nor for the band: per (32-channel tile, key tile) the wave stages ONE 32 x 32
+//                     block transposed (tlong_key_pos swap, zero-filled beyond the clip and beyond head_dim) into its OWN 2.5 KB of
+//                     LDS, reads the two A fragments back and moves on.  Wave-private: no workgroup barrier anywhere in the kernel, and
+//                     10 KB of LDS per workgroup whatever the clip, the window and the head dimension.
+// Work follows F (2 W + 1): Fq / 32 query tiles x NT key tiles.  One workgroup = one (batch element, token, group of `hg` heads,
+// four consecutive 32-query tiles): wave w owns tile 4 qg + w and walks the group's heads; the waves of a workgroup share their
+// overlapping K / V rows (and the heads of a token their cache lines) through L1.
+#define TBAND_LDV 40  // halves between channel rows of a wave's Vt block: 20 dwords, 16 lanes of a ds_read_b128 on 16 distinct bank quads
+struct TemporalBandArgs {
+    const half_t *q, *k, *v;
+    half_t* o;
+    int F, Fq, q0, W, tokens, heads, dh;
+    int hg, ngroups, nqg;  // heads per workgroup, head groups per token, groups of four query tiles
+    int64_t in_stride, q_stride, out_stride;
+    float scale;
+};
+
+template <int NT>
+FZ_KERNEL void __launch_bounds__(TTHREADS) attn_temporal_band_kernel(TemporalBandArgs a) {
+    FZ_DYN_SMEM(raw);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = fz_uniform(tid >> 6);
+    half_t* Vt = reinterpret_cast<half_t*>(raw) + wave * (32 * TBAND_LDV);  // [32 channels][TBAND_LDV], this wave's own
+    const int b = blockIdx.y;
+    int bx = blockIdx.x;
+    const int qg = bx % a.nqg;
+    bx /= a.nqg;
+    const int h0 = (bx % a.ngroups) * a.hg;
+    const int tok = bx / a.ngroups;
+    const int qt = qg * (TTHREADS / 64) + wave;
+    if (qt * 32 >= a.Fq) return;  // wave-uniform; the kernel has no workgroup barrier
+    const int F = a.F, dh = a.dh, W = a.W;
+    const int i = lane & 31, hi = lane >> 5;
+    const int qf = qt * 32 + i;
+    const bool qok = qf < a.Fq;
+    const int qabs = a.q0 + (qok ? qf : a.Fq - 1);  // (a lane beyond q_frames mirrors the last query: a non-empty band, nothing stored)
+    const int a0 = a.q0 + qt * 32;                  // absolute frame of the tile's first query
+    const int alast = (qt * 32 + 31 < a.Fq ? qt * 32 + 31 : a.Fq - 1) + a.q0;
+    const int t0 = (a0 - W > 0 ? a0 - W : 0) >> 5;                 // first (aligned) key tile of the band
+    const int kend = alast + W + 1 < F ? alast + W + 1 : F;        // keys >= kend: beyond the band of every query here, or the clip
+    const int klo = qabs - W, khi = qabs + W < F - 1 ? qabs + W : F - 1;  // this lane's band [klo, khi] (klo may be negative)
+    const int64_t kv_frame = (int64_t)a.tokens * a.in_stride;      // halves between the same token of consecutive frames
+    const int64_t qo_row = ((int64_t)b * a.Fq + (qok ? qf : 0)) * a.tokens + tok;
+    const half_t* kbase = a.k + ((int64_t)b * F * a.tokens + tok) * a.in_stride;  // frame 0 of this batch element
+    const half_t* vbase = a.v + ((int64_t)b * F * a.tokens + tok) * a.in_stride;
+    for (int hl = 0; hl < a.hg; ++hl) {
+        const int col = (h0 + hl) * dh;
+        const half_t* qrow = a.q + qo_row * a.q_stride + col;
+        // ---- S^T = K Q^T over the band's key tiles
+        f32x16 s[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) s[t] = fz_zero_f16v();
+        for (int c0 = 0; c0 < dh; c0 += 16) {
+            const int ch = c0 + 8 * hi;
+            const bool chok = ch < dh;
+            const half8_t qfrag = (qok && chok) ? fz_ld_h8(qrow + ch) : fz_zero_h8();
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (32 * (t0 + t) >= kend) continue;  // wave-uniform
+                const int key = 32 * (t0 + t) + i;
+                const half8_t kfrag = (key < kend && chok) ? fz_ld_h8(kbase + key * kv_frame + col + ch) : fz_zero_h8();
+                s[t] = fz_mfma_32x32x16_f16(kfrag, qfrag, s[t]);
+            }
+        }
+        // ---- exact softmax over the band of query qabs
+        float mx = -1e30f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = 32 * (t0 + t) + 8 * (r >> 2) + 4 * hi + (r & 3);
+                const float x = (key >= klo && key <= khi) ? s[t][r] * a.scale : -1e30f;
+                s[t][r] = x;
+                mx = fmaxf(mx, x);
+            }
+        mx = fz_pair_max32(mx);
+        float sum = 0.0f;
+        {
+#ifndef FZ_EMU
+#pragma clang fp reassociate(off)
+#endif
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    // (a masked slot holds -1e30 and mx is a real score -- the band is never empty: its exp is exactly 0, and the
+                    // 16 NT lane masks of the first sweep need not be kept alive for this one)
+                    const float e = __builtin_expf(s[t][r] - mx);
+                    s[t][r] = e;
+                    sum = sum + e;
+                }
+        }
+        sum += fz_shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        half8_t p[NT][2];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) p[t][r >> 3][r & 7] = (half_t)(s[t][r] * inv);  // P is cast to fp16 before P.V
+        // ---- O^T = V^T P^T, one 32-channel tile at a time, V block by block through the wave's own LDS
+        half_t* orow = a.o + qo_row * a.out_stride + col;
+        for (int c0 = 0; c0 < dh; c0 += 32) {
+            f32x16 acc = fz_zero_f16v();
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (32 * (t0 + t) >= kend) continue;  // wave-uniform
+                const int key = 32 * (t0 + t) + i;
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {
+                    const int cv = 2 * it + hi;  // 8-channel chunk of the 32-channel tile
+                    half8_t vv = fz_zero_h8();
+                    if (key < F && c0 + 8 * cv < dh) vv = fz_ld_h8(vbase + key * kv_frame + col + c0 + 8 * cv);
+                    half_t* dst = Vt + (8 * cv) * TBAND_LDV + tlong_key_pos(i);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) dst[e * TBAND_LDV] = vv[e];
+                }
+                fz_wave_lds_sync();  // the block is written by the wave's lanes and read back by other lanes of the same wave
+#pragma unroll
+                for (int kc = 0; kc < 2; ++kc) {
+                    const half8_t vfrag = fz_ld_h8(Vt + i * TBAND_LDV + 8 * hi + 16 * kc);
+                    acc = fz_mfma_32x32x16_f16(vfrag, p[t][kc], acc);
+                }
+                fz_wave_lds_sync();  // ... and is overwritten by the next block only after these reads
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ch = c0 + 8 * g + 4 * hi;
+                if (qok && ch < dh) {
+                    half4_t ov;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ov[r] = (half_t)acc[4 * g + r];
+                    *reinterpret_cast<half4_t*>(orow + ch) = ov;
+                }
+            }
+        }
+    }
+}
+
+static_assert(FZ_TEMPORAL_MAX_WINDOW == 96, "the band kernel's instantiations end at 8 key tiles: ceil((32 + 2 W) / 32) + 1 <= 8");
+
+// heads per workgroup of the band kernel: all of them (the heads of a token share cache lines), halved while the grid would leave
+// most of the chip idle -- a head's result does not depend on the grouping
+static int tband_launch(const TemporalBandArgs& a0, int batch, void* stream) {
+    TemporalBandArgs a = a0;
+    const int nt = (32 + 2 * a.W + 31) / 32 + 1;
+    a.nqg = ((a.Fq + 31) / 32 + TTHREADS / 64 - 1) / (TTHREADS / 64);
+    a.hg = a.heads;
+    while (a.hg % 2 == 0 && (int64_t)a.tokens * (a.heads / a.hg) * a.nqg * batch < 2048) a.hg /= 2;
+    a.ngroups = a.heads / a.hg;
+    if ((int64_t)a.tokens * a.ngroups * a.nqg > 0x7fffffff || batch > 65535) return FZ_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)(TTHREADS / 64) * 32 * TBAND_LDV * sizeof(half_t);
+    dim3 grid((unsigned)(a.tokens * a.ngroups * a.nqg), batch), block(TTHREADS);
+    auto launch = [&](auto kern) -> int { return FZ_LAUNCH_LDS(kern, grid, block, lds, stream, a); };
+    switch (nt) {
+        case 2: return launch(attn_temporal_band_kernel<2>);
+        case 3: return launch(attn_temporal_band_kernel<3>);
+        case 4: return launch(attn_temporal_band_kernel<4>);
+        case 5: return launch(attn_temporal_band_kernel<5>);
+        case 6: return launch(attn_temporal_band_kernel<6>);
+        case 7: return launch(attn_temporal_band_kernel<7>);
+        case 8: return launch(attn_temporal_band_kernel<8>);
+    }
+    return FZ_ERR_BAD_ARG;
+}
+
+extern "C" int fz_attn_temporal_win(const void* q, const void* k, const void* v, void* o, int batch, int q_frames, int kv_frames,
+                                    int q_frame0, int window, int tokens, int heads, int head_dim, int64_t q_row_stride,
+                                    int64_t kv_row_stride, int64_t o_row_stride, float scale, void* stream) {
+    if (!q || !k || !v || !o || batch <= 0 || q_frames <= 0 || kv_frames <= 0 || kv_frames > TSTREAM_MAXF || window < 0 ||
+        q_frame0 < 0 || (int64_t)q_frame0 + q_frames > kv_frames || tokens <= 0 || heads <= 0 || head_dim <= 0)
+        return FZ_ERR_BAD_ARG;
+    if ((head_dim & 7) || (q_row_stride & 7) || (kv_row_stride & 7) || (o_row_stride & 7)) return FZ_ERR_BAD_ARG;
+    if (window >= kv_frames - 1)  // the window covers the clip for every query: today's launch, bit for bit
+        return fz_attn_temporal_ex(q, k, v, o, batch, q_frames, kv_frames, tokens, heads, head_dim, q_row_stride, kv_row_stride,
+                                   o_row_stride, scale, stream);
+    if (kv_frames > TMAXF) {
+        if (window > FZ_TEMPORAL_MAX_WINDOW) return FZ_ERR_UNSUPPORTED;
+        TemporalBandArgs t;
+        t.q = (const half_t*)q; t.k = (const half_t*)k; t.v = (const half_t*)v; t.o = (half_t*)o;
+        t.F = kv_frames; t.Fq = q_frames; t.q0 = q_frame0; t.W = window; t.tokens = tokens; t.heads = heads; t.dh = head_dim;
+        t.hg = t.ngroups = t.nqg = 0;
+        t.in_stride = kv_row_stride; t.q_stride = q_row_stride; t.out_stride = o_row_stride; t.scale = scale;
+        return tband_launch(t, batch, stream);
+    }
+    TemporalWinArgs a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.v = (const half_t*)v; a.o = (half_t*)o;
+    a.batch = batch; a.F = kv_frames; a.Fq = q_frames; a.q0 = q_frame0; a.W = window; a.tokens = tokens; a.heads = heads; a.dh = head_dim;
+    a.ns = 2 * window + 1 < kv_frames ? 2 * window + 1 : kv_frames;
+    a.in_stride = kv_row_stride; a.q_stride = q_row_stride; a.out_stride = o_row_stride; a.scale = scale;
+    int tpb = TTHREADS / (heads * q_frames);
+    if (tpb < 1) tpb = 1;
+    a.tok_per_block = tpb;
+    if (batch > 65535) return FZ_ERR_UNSUPPORTED;
+    dim3 grid((tokens + tpb - 1) / tpb, batch), block(TTHREADS);
+    return FZ_LAUNCH_LDS(attn_temporal_win_kernel, grid, block, (size_t)TTHREADS * a.ns * sizeof(float), stream, a);
+}

@@ -304,6 +304,12 @@ class IssuePlans:
             self._sc_blocks = [m for m in self.unet.modules() if isinstance(m, SpatioTemporalTransformerBlock)]
         return tuple(tuple(b.sc_index) for b in self._sc_blocks)
 
+    def _temporal_windows(self):
+        """The temporal_attention_window of every transformer block, read like _sc_lists: another window is another kernel, grid and
+        argument block in every temporal-attention record."""
+        self._sc_lists()
+        return tuple(b.temporal_window for b in self._sc_blocks)
+
     def clear(self):
         self.seen.clear()
         self.plans.clear()
@@ -322,7 +328,8 @@ class IssuePlans:
         return (tuple(x.data.shape), x.b, x.rep, x.f, x.h, x.w, str(x.data.device), K._scratch_key(x.data)[1], tuple(temb_act.shape), tuple(ctx.shape),
                 ctx.dtype, type(controller), sig, _model_switches(),  # (sig carries the map format)
                 getattr(self.unet, "_maps_up_to", None),  # (a forward that ends behind its last captured map is another launch list)
-                self._sc_lists())  # (another index list is another n_kv in every self-attention record)
+                self._sc_lists(),  # (another index list is another n_kv in every self-attention record)
+                self._temporal_windows())
 
     # -- record --------------------------------------------------------------------------------------------
     @classmethod

@@ -19,6 +19,7 @@ MAP8_FORMATS = ("e5m2", "ue4m4")  # what a torch.uint8 map may hold: the tensor 
 CROSS_P_STRIDE = N.FZ_CROSS_P_STRIDE
 CROSS_KEYS = N.FZ_CROSS_MAX_KEYS
 TEMPORAL_MAX_FRAMES = N.FZ_TEMPORAL_MAX_FRAMES
+TEMPORAL_MAX_WINDOW = N.FZ_TEMPORAL_MAX_WINDOW
 MAX_KV_SLOTS = N.FZ_MAX_KV_SLOTS
 SUPPORTED_HEAD_DIMS = (16, 32, 40, 64, 80, 128, 160)
 
@@ -253,22 +254,51 @@ def attn_cross(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Te
     return out
 
 
+def check_temporal_window(window, kv_frames: Optional[int] = None) -> None:
+    """`model_config.temporal_attention_window`: None (every frame) or a non-negative int.  With the clip length known, a window the
+    band kernel cannot serve (above TEMPORAL_MAX_WINDOW on a clip of more than 64 frames, and not covering the clip) is refused too."""
+    if window is None:
+        return
+    if isinstance(window, bool) or not isinstance(window, int) or window < 0:
+        raise ValueError("temporal_attention_window must be None or a non-negative int, got %r" % (window,))
+    if kv_frames is not None and kv_frames > 64 and TEMPORAL_MAX_WINDOW < window < kv_frames - 1:
+        raise ValueError("temporal attention serves windows of up to %d frames on either side (FZ_TEMPORAL_MAX_WINDOW = %d) on clips "
+                         "of more than 64 frames, or a window that covers the clip; got window %d on %d key/value frames"
+                         % (TEMPORAL_MAX_WINDOW, TEMPORAL_MAX_WINDOW, window, kv_frames))
+
+
 def attn_temporal(q, k, v, out, *, batch: int, clip_len: int, heads: int, scale: Optional[float] = None,
-                  kv_frames: Optional[int] = None):
+                  kv_frames: Optional[int] = None, window: Optional[int] = None, q_frame0: int = 0):
     """q,out: [B*clip_len, tokens, >=C]; k,v: [B*kv_frames, tokens, >=C] token-major views (kv_frames defaults to clip_len;
     it is larger when the clip is frame-sharded and k / v were all-gathered).  Neither may exceed TEMPORAL_MAX_FRAMES (512): the
     larger of the two picks the kernel -- up to 64 one thread per query frame, up to 256 whole score rows in registers, beyond that
-    the streaming kernel (keys in chunks of 256, head_dim <= 160).  A longer clip is a ValueError that names the limit."""
+    the streaming kernel (keys in chunks of 256, head_dim <= 160).  A longer clip is a ValueError that names the limit.
+
+    window: None -- every query frame attends all kv_frames (the call above, unchanged); W >= 0 -- row i of q is frame q_frame0 + i
+    of the kv_frames and attends the frames within W of it (fz_attn_temporal_win; W >= kv_frames - 1 is the unwindowed launch).
+    Above TEMPORAL_MAX_WINDOW on a clip of more than 64 frames: a ValueError that names the limit."""
     _, tokens, c = q.shape
     d_head = c // heads
     kv_frames = clip_len if kv_frames is None else kv_frames
     if max(clip_len, kv_frames) > TEMPORAL_MAX_FRAMES:
         raise ValueError("temporal attention serves clips of up to %d frames (FZ_TEMPORAL_MAX_FRAMES); got %d query and %d "
                          "key/value frames" % (TEMPORAL_MAX_FRAMES, clip_len, kv_frames))
+    if window is not None:
+        check_temporal_window(window, kv_frames)
+        if isinstance(q_frame0, bool) or not isinstance(q_frame0, int) or q_frame0 < 0 or q_frame0 + clip_len > kv_frames:
+            raise ValueError("q_frame0 = %r: the %d query frames must lie inside the %d key/value frames" % (q_frame0, clip_len, kv_frames))
+    elif q_frame0 != 0:
+        raise ValueError("q_frame0 has a meaning only with a window")
     _chk16(q, k, v, out)
     assert k.stride(1) == v.stride(1) and q.stride(0) == tokens * q.stride(1) and k.stride(0) == tokens * k.stride(1)
     assert v.stride(0) == tokens * v.stride(1) and out.stride(0) == tokens * out.stride(1)
     assert q.shape[0] == batch * clip_len and k.shape[0] == batch * kv_frames
+    if window is not None:
+        N.check(N.lib().fz_attn_temporal_win(_ptr(q), _ptr(k), _ptr(v), _ptr(out), batch, clip_len, kv_frames, q_frame0,
+                                             min(window, 0x7fffffff), tokens, heads, d_head, q.stride(1), k.stride(1), out.stride(1),
+                                             float(scale if scale is not None else d_head ** -0.5), _stream(q)),
+                "fz_attn_temporal_win")
+        return out
     N.check(N.lib().fz_attn_temporal_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), batch, clip_len, kv_frames, tokens, heads,
                                         d_head, q.stride(1), k.stride(1), out.stride(1),
                                         float(scale if scale is not None else d_head ** -0.5), _stream(q)),

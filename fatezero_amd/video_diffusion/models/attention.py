@@ -269,8 +269,9 @@ class CrossAttention(nn.Module):
         return _out_proj(self.to_out[0], out, residual, ln_next)
 
     # -- temporal attention (attention.py:327-337; never controlled, attention_register.py:242) ---------------
-    def forward_temporal(self, x_norm, batch: int, clip: int, residual=None):
-        """x_norm: [B*F, L, C] LayerNorm'ed; attention over the F frames of every (b, token); + residual in the epilogue."""
+    def forward_temporal(self, x_norm, batch: int, clip: int, residual=None, window=None):
+        """x_norm: [B*F, L, C] LayerNorm'ed; attention over the F frames of every (b, token); + residual in the epilogue.
+        window: the block's `model_config.temporal_attention_window` -- None: every frame; W: the frames within W of the query's."""
         n, l, c = x_norm.shape
         if self._qkv is None or self._qkv.device != x_norm.device:
             self._qkv = torch.cat([self._qk_weight(x_norm.dtype, x_norm.device),
@@ -286,13 +287,15 @@ class CrossAttention(nn.Module):
             q = K.gemm(x_norm, self._qkv[:inner])
             kv = pend.wait().reshape(batch * shard.clip_len, l, 2 * inner)
             out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
+            # (a window keeps the all-gather: every rank still receives all frames' K | V and reads the band around its own)
+            win = {} if window is None else dict(window=window, q_frame0=shard.frames_of(shard.rank).start)
             K.attn_temporal(q, kv[..., :inner], kv[..., inner:], out, batch=batch, clip_len=clip,
-                            kv_frames=shard.clip_len, heads=self.heads, scale=self.scale)
+                            kv_frames=shard.clip_len, heads=self.heads, scale=self.scale, **win)
             return self.to_out[0].apply(out, res=residual)
         qkv = K.gemm(x_norm, self._qkv)
         out = torch.empty(n, l, inner, dtype=x_norm.dtype, device=x_norm.device)
         K.attn_temporal(qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:], out, batch=batch, clip_len=clip,
-                        heads=self.heads, scale=self.scale)
+                        heads=self.heads, scale=self.scale, **({} if window is None else dict(window=window)))
         return self.to_out[0].apply(out, res=residual)
 
     def load_state_dict(self, *a, **k):  # packed weights / cached projections must follow the parameters
@@ -497,6 +500,7 @@ class SpatioTemporalTransformerBlock(nn.Module):
         if "least_sc_channel" in model_config and dim < model_config["least_sc_channel"]:
             self.model_config["SparseCausalAttention_index"] = []  # attention.py:171-173
         K.check_kv_slot_count(self.sc_index)  # a list the kernels cannot serve fails here, before any checkpoint is read
+        K.check_temporal_window(self.temporal_window)  # (the limit depends on the clip length: kernels.attn_temporal checks it per call)
         self.attn1 = SparseCausalAttention(query_dim=dim, heads=num_attention_heads, dim_head=attention_head_dim)
         self.norm1 = _NormParams(dim)
         self.attn2 = CrossAttention(query_dim=dim, cross_attention_dim=cross_attention_dim, heads=num_attention_heads,
@@ -511,6 +515,10 @@ class SpatioTemporalTransformerBlock(nn.Module):
     @property
     def sc_index(self):
         return self.model_config.get("SparseCausalAttention_index", [-1, "first"])  # attention.py:347 default
+
+    @property
+    def temporal_window(self):
+        return self.model_config.get("temporal_attention_window")  # None: temporal attention over every frame of the clip
 
     def forward_tokens(self, x: Tokens, ctx, prenorm1=None):
         """x.rep > 1 (the CFG-shared head): x.data / prenorm1 hold x.nb batch elements.  The shared part ends at attn2 -- the first op that reads
@@ -545,7 +553,7 @@ class SpatioTemporalTransformerBlock(nn.Module):
         hs, nt = self.ff.apply(n3, res=hs, ln_next=self.norm_temporal if lnp else None)
         if nt is None:
             nt = layer_norm_tokens(self.norm_temporal, hs)
-        hs = self.attn_temporal.forward_temporal(nt, x.b, clip, residual=hs)
+        hs = self.attn_temporal.forward_temporal(nt, x.b, clip, residual=hs, window=self.temporal_window)
         return x.like(hs)
 
 

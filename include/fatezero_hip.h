@@ -148,6 +148,24 @@ int fz_attn_temporal_ex(const void* q, const void* k, const void* v, void* o, in
                         int tokens, int heads, int head_dim, int64_t q_row_stride, int64_t kv_row_stride,
                         int64_t o_row_stride, float scale, void* stream);
 
+/* Largest window fz_attn_temporal_win serves on clips of more than 64 frames (below that every window is served).  The band kernel
+ * keeps the key tiles aligned to absolute multiples of 32 frames, so a 32-query tile at any q_frame0 touches at most
+ * ceil((32 + 2 W) / 32) + 1 of them: 8 at W = 96, the tile count whose score rows fit the register file without scratch. */
+#define FZ_TEMPORAL_MAX_WINDOW 96
+
+/* Windowed temporal attention: fz_attn_temporal_ex where query frame f attends only the key/value frames j with |j - f| <= window,
+ * cut at the clip's ends (nothing is padded; window 0 returns V of the same frame).  f is an ABSOLUTE index among the kv_frames:
+ * row i of q/o is frame q_frame0 + i (a frame-sharded rank passes the start of its own frames; 0 otherwise).  Scores in fp32, exact
+ * softmax over the attended keys, P normalised and then rounded to fp16, as in the unwindowed entries; a query's result does not
+ * depend on q_frame0 or on which other query frames share the launch.
+ * Domain: window >= 0, q_frame0 >= 0, q_frame0 + q_frames <= kv_frames <= FZ_TEMPORAL_MAX_FRAMES, head_dim % 8 == 0, row strides
+ * % 8 == 0; FZ_ERR_BAD_ARG outside it.  window >= kv_frames - 1 IS fz_attn_temporal_ex (same launch, same bits).  kv_frames <= 64:
+ * one thread per query frame, any window; beyond: the matrix-pipe band kernel, whose work follows kv_frames * (2 window + 1) --
+ * a window above FZ_TEMPORAL_MAX_WINDOW (and below kv_frames - 1) is FZ_ERR_UNSUPPORTED. */
+int fz_attn_temporal_win(const void* q, const void* k, const void* v, void* o, int batch, int q_frames, int kv_frames,
+                         int q_frame0, int window, int tokens, int heads, int head_dim, int64_t q_row_stride,
+                         int64_t kv_row_stride, int64_t o_row_stride, float scale, void* stream);
+
 /* Blend mask (SpatialBlender.get_mask, spatial_blend.py:24-56): maps: n_maps pointers to fp16 cross maps
  * [P][F][heads][r*r][p_row_stride] (P = n_prompts, prompt stride given), alpha: float [P][80] word weights;
  * out: float [P][F][h][w] of 0/1 after 3x3 max-pool, nearest resize, per-(P,F) max normalisation, > th.

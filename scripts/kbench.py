@@ -211,6 +211,32 @@ def temporal_stream_bench():
             del qkv, out
 
 
+def temporal_window_bench(windows=(8, 16, 32)):
+    """Windowed temporal attention (attn_temporal_band_kernel) at F = 512, CFG batch 2, the four SD-1.x levels, W = 8 / 16 / 32.  The
+    yardstick is the UNWINDOWED launch (attn_temporal_stream_kernel) timed in the same process on the same buffers.  `floor us`: q, k, v
+    read and o written once at 4 TB/s.  No gate."""
+    dev, f = "cuda", 512
+    print("temporal attention launch times, F = 512, batch 2, q / k / v column slices of a packed 3C buffer; ~0.2 s of back-to-back launches per shape")
+    print("%-14s %7s %12s %14s %7s %10s" % ("(tokens, C)", "W", "us", "unwindowed us", "ratio", "floor us"))
+    for (tokens, c) in [(4096, 320), (1024, 640), (256, 1280), (64, 1280)]:
+        qkv = torch.randn(2 * f, tokens, 3 * c, device=dev, dtype=torch.float16)
+        out = torch.empty(2 * f, tokens, c, dtype=torch.float16, device=dev)
+
+        def run(window=None):
+            K.attn_temporal(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], out, batch=2, clip_len=f, heads=8, window=window)
+
+        def t(fn):
+            ms = timeit(fn, iters=10, warm=3)
+            return timeit(fn, iters=max(10, min(1000, int(200.0 / ms))), warm=0)
+        base = t(run)
+        floor_us = 4.0 * 2 * f * tokens * c * 2 / 4e12 * 1e6
+        print("%-14s %7s %12.1f %14s %7s %10.1f" % ((tokens, c), "-", base * 1e3, "-", "-", floor_us))
+        for w in windows:
+            ms = t(lambda: run(w))
+            print("%-14s %7d %12.1f %14.1f %7.2f %10.1f" % ((tokens, c), w, ms * 1e3, base * 1e3, ms / base, floor_us))
+        del qkv, out
+
+
 def norms_bench():
     dev, res, F_ = "cuda", {}, 8
     for (n, tokens, c) in [(8, 4096, 320), (16, 4096, 320), (8, 4096, 640), (8, 4096, 960), (8, 1024, 640), (8, 1024, 1920),
@@ -281,6 +307,8 @@ def main():
         return conv64_bench()
     if "--norms" in sys.argv:
         return norms_bench()
+    if "--temporal-window" in sys.argv:
+        return temporal_window_bench()
     if "--temporal-stream" in sys.argv:
         return temporal_stream_bench()
     if "--temporal-long" in sys.argv:
